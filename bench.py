@@ -33,8 +33,15 @@ so that a CPU-share limit on a shared node can be told from a code change.
 ``M2K_HOST_THREADS=1`` sizes every host pool to one thread
 (``scripts/scale_rehearsal.sh`` runs the three variants).
 
-Correctness (untimed, rank 0): ``manifest_diff_vs_ref`` is the number of
-files that differ from the reference-derived expected trees
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line; everything below marked ``--full`` is skipped and its fields are null.
+
+``--dump-outputs DIR`` (rank 0): what the last timed step wrote, as float
+arrays, so that two builds can be compared output for output
+(:func:`dump_outputs`).
+
+Correctness (``--full``, untimed, rank 0): ``manifest_diff_vs_ref`` is the
+number of files that differ from the reference-derived expected trees
 (``tests/golden/reference/<config>``) over all five configurations, and
 ``per_config`` gives each configuration's diff plus its warm in-process and
 cold CLI-process p50 and interquartile range over ``--check-runs`` (default 9)
@@ -137,6 +144,40 @@ def large_tree_check(sizes):
             "ratio_largest_vs_smallest": round(rows[-1]["ms_per_service"] / rows[0]["ms_per_service"], 3)}
 
 
+DUMP_LIMIT = 64 << 20  # bytes over all dumped arrays
+
+
+def dump_outputs(out_root, work, dirpath):
+    """``--dump-outputs``: the output tree a step wrote (what a caller of
+    ``translate`` receives), as ``.npy`` arrays under ``dirpath``.  Files in
+    sorted order of their relative path:
+
+    * ``tree_bytes.npy`` (float32): every file's bytes, concatenated, one
+      value per byte, the work directory's path read as ``$WORK``;
+    * ``tree_file_sizes.npy`` (float64): each file's length in that array;
+    * ``tree_paths.npy`` (float32): the bytes of the newline-joined paths.
+
+    The inputs are the committed corpus and QA cache, so the arrays are the
+    same from run to run.  A tree too large for ``DUMP_LIMIT`` is cut to a
+    fixed, seeded sample of its byte positions."""
+    import numpy as np
+    files = tree_files(out_root)
+    rels = sorted(files)
+    blobs = []
+    for rel in rels:
+        with open(files[rel], "rb") as f:
+            blobs.append(f.read().replace(os.fsencode(work), refconfigs.WORK_PLACEHOLDER))
+    data = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+    paths = np.frombuffer("\n".join(rels).encode("utf-8", "surrogateescape"), dtype=np.uint8)
+    room = (DUMP_LIMIT - 4 * paths.size - 8 * len(rels)) // 4 - 64   # .npy headers
+    if data.size > room:
+        data = data[np.sort(np.random.default_rng(0).choice(data.size, max(0, room), replace=False))]
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "tree_bytes.npy"), data.astype(np.float32))
+    np.save(os.path.join(dirpath, "tree_file_sizes.npy"), np.array([len(b) for b in blobs], dtype=np.float64))
+    np.save(os.path.join(dirpath, "tree_paths.npy"), paths.astype(np.float32))
+
+
 def step_spread(step_s):
     """Rank 0's per-step wall times: min / p50 / p90 / max in ms, so that box
     noise (a slow tail) can be told from a regression (a shifted p50)."""
@@ -220,19 +261,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default=refconfigs.HEADLINE,
                     choices=sorted(refconfigs.CONFIGS) + sorted(refconfigs.EXTRA_CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed checks: every configuration's diff against its expected tree, "
+                         "warm/cold runs per configuration, large synthetic trees, one traced step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its output tree) as DIR/<name>.npy")
     ap.add_argument("--check-runs", type=int, default=9,
-                    help="warm/cold runs per configuration in the untimed per-config check (0 = skip)")
+                    help="with --full: warm/cold runs per configuration in the untimed per-config check (0 = skip)")
     ap.add_argument("--prev", default=PREV_BENCH,
-                    help="previous round's bench line (JSON) for per_config_vs_prev; empty = skip")
+                    help="with --full: previous round's bench line (JSON) for per_config_vs_prev; empty = skip")
     ap.add_argument("--pin-cores", action="store_true",
                     help="rehearsal knob: pin each rank to its own physical cores (LOCAL_RANK) before any GPU call")
     ap.add_argument("--large-tree", default="100,1000,5000",
-                    help="untimed: translate synthetic trees of these app counts and report ms per service "
+                    help="with --full, untimed: translate synthetic trees of these app counts and report ms per service "
                          "(benchmarks/translate_large_tree.py); empty = skip")
     ap.add_argument("--keep", action="store_true", help="keep the work directory")
     ap.add_argument("--workdir", default="auto",
                     help="root for the input copies and output trees: auto (tmpfs if available), disk, or a path")
     args = ap.parse_args()
+    dump_dir = os.path.abspath(args.dump_outputs) if args.dump_outputs else None
 
     world, rank, local_rank = _dist_env()
     pinned = None
@@ -271,9 +318,9 @@ def main():
     phase_ms = None
     try:
         with run.session() as s:
-            out = run.step(s)  # first (warm-up) step doubles as the correctness gate
+            out = run.step(s)  # first (warm-up) step; with --full it doubles as the correctness gate
             n_services = len(s.plan(run.src, refconfigs.PROJECT).services)
-            if rank == 0:
+            if rank == 0 and args.full:
                 diff_headline = refconfigs.manifest_diff_vs_ref(args.config, out)
             for _ in range(max(0, args.warmup - 1)):
                 run.step(s)
@@ -289,7 +336,9 @@ def main():
             elapsed = time.perf_counter() - t0
             cpu1, thr1 = _cpu_s(), _cgroup_throttled_us()
             cpu_s = tuple(b - a for a, b in zip(cpu0, cpu1))
-            if rank == 0:
+            if rank == 0 and dump_dir:
+                dump_outputs(out, run.work, dump_dir)   # the tree the last timed step wrote
+            if rank == 0 and args.full:
                 # untimed: one traced step for the per-phase breakdown (utils/trace.py)
                 from move2kube_amd.utils import trace
                 trace.enable("")
@@ -304,9 +353,9 @@ def main():
             shutil.rmtree(work, ignore_errors=True)
 
     per_config = None
-    if rank == 0 and args.check_runs > 0:
+    if rank == 0 and args.full and args.check_runs > 0:
         per_config = per_config_checks(args.check_runs)
-    if rank == 0 and args.large_tree:
+    if rank == 0 and args.full and args.large_tree:
         per_config = dict(per_config or {})
         per_config["large-tree"] = large_tree_check([int(x) for x in args.large_tree.split(",")])
 
@@ -342,6 +391,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms, 3),
             "step_ms": spread,
             # host-side accounting of the timed region, to tell a CPU-share

@@ -1,5 +1,5 @@
 # One pass on the GPU box into gpurun_out/$RUN/:
-#   pytest -m gpu, smoke(), bench.py with its default checks (per-config diffs,
+#   pytest -m gpu, smoke(), bench.py --full with its checks (per-config diffs,
 #   warm/cold p50s, large-tree ratio), rocprofv3 kernel stats of smoke(), and,
 #   when AB names a tree under .ab_base/, the interleaved same-box A/B of the
 #   headline against it (benchmarks/ab_bench.py).
@@ -25,7 +25,7 @@ tail -1 "$OUT/pytest_gpu.log"
 echo "smoke"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 echo "bench"
-timeout -k 10 600 python -u bench.py > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.log" 2>&1
 grep '^{' "$OUT/bench.log" > "$OUT/bench.json"
 python -c 'import json,sys; d=json.load(open(sys.argv[1])); print(d["ms_per_step"], d["step_ms"], d["manifest_diff_vs_ref"], d["per_config"]["large-tree"]["ratio_largest_vs_smallest"])' "$OUT/bench.json"
 echo "rocprof smoke"

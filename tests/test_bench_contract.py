@@ -42,7 +42,7 @@ def _last_json(stdout):
 @needs_torch
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="CPU-only contract test")
 def test_single_rank():
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--check-runs", "1",
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "1", "--check-runs", "1",
                         "--large-tree", "20,60"], cwd=ROOT,
                        env=_env(),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -69,6 +69,47 @@ def test_single_rank():
     # the headline names BASELINE.json configuration 5 verbatim
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         assert d["config"]["model"] in json.load(f)["configs"]
+
+
+@needs_torch
+@pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="CPU-only contract test")
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """Without --full the run only times its steps (every untimed check's
+    field is null) and --dump-outputs writes the last step's output tree as
+    float arrays: the same from run to run, and byte for byte the expected
+    tree of the headline configuration."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "benchmarks"))
+    import refconfigs
+    dumps = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / name)], cwd=ROOT, env=_env(),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        d = _last_json(p.stdout.decode())
+        assert KEYS <= set(d) and d["full"] is False
+        assert d["steps"] == 2 and d["step_ms"]["n"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+        for k in ("manifest_diff_vs_ref", "manifest_diff_vs_ref_headline", "per_config", "per_config_vs_prev",
+                  "phase_ms_one_step"):
+            assert d[k] is None, k
+        assert sorted(os.listdir(tmp_path / name)) == ["tree_bytes.npy", "tree_file_sizes.npy", "tree_paths.npy"]
+        dumps.append({k: np.load(tmp_path / name / (k + ".npy")) for k in ("tree_bytes", "tree_file_sizes",
+                                                                          "tree_paths")})
+    a, b = dumps
+    assert a["tree_bytes"].dtype == np.float32 and a["tree_file_sizes"].dtype == np.float64
+    assert a["tree_paths"].dtype == np.float32
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    golden = refconfigs.tree_files(refconfigs.golden_dir(refconfigs.HEADLINE))
+    rels = sorted(golden)
+    assert bytes(a["tree_paths"].astype(np.uint8)).decode() == "\n".join(rels)
+    want = []
+    for rel in rels:
+        with open(golden[rel], "rb") as f:
+            want.append(f.read())
+    assert a["tree_file_sizes"].tolist() == [float(len(w)) for w in want]
+    assert bytes(a["tree_bytes"].astype(np.uint8)) == b"".join(want)
 
 
 @needs_torch

@@ -78,8 +78,19 @@ class _UnixServer(socketserver.ThreadingMixIn, socketserver.UnixStreamServer):
 
 
 @pytest.fixture
-def fake_dockerd(tmp_path, monkeypatch):
-    sock = str(tmp_path / "docker.sock")
+def sock_dir():
+    """A short directory for a fake daemon's socket: a unix socket address
+    holds at most 107 bytes, and ``tmp_path`` under a deep TMPDIR is longer."""
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="m2k-sock-", dir="/tmp" if os.access("/tmp", os.W_OK) else None)
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
+def fake_dockerd(sock_dir, monkeypatch):
+    sock = os.path.join(sock_dir, "docker.sock")
     srv = _UnixServer(sock, _FakeDockerd)
     t = threading.Thread(target=srv.serve_forever, daemon=True)
     t.start()
@@ -384,8 +395,8 @@ class _NoBindDockerd(_FakeDockerd):
 
 
 @pytest.fixture
-def nobind_dockerd(tmp_path, monkeypatch):
-    sock = str(tmp_path / "docker.sock")
+def nobind_dockerd(sock_dir, monkeypatch):
+    sock = os.path.join(sock_dir, "docker.sock")
     srv = _UnixServer(sock, _NoBindDockerd)
     t = threading.Thread(target=srv.serve_forever, daemon=True)
     t.start()

@@ -35,7 +35,10 @@ def test_threads_and_cli_processes_are_counted(tmp_path):
         "                   stdout=subprocess.DEVNULL)\n")
     data = tmp_path / "data"
     out = tmp_path / "out"
-    res = m2kcov.run([str(probe), "-q", "-p", "no:cacheprovider"], str(out), keep_data=str(data))
+    # --rootdir: pytest runs in the repository and would otherwise collect from
+    # the common ancestor of both directories, which it may not be able to list
+    res = m2kcov.run([str(probe), "-q", "-p", "no:cacheprovider", "--rootdir", str(tmp_path)], str(out),
+                     keep_data=str(data))
     assert res["pytest_exit"] == 0
     assert res["processes"] >= 2           # pytest and the CLI process
     mods = res["modules"]
