@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """GPU vs native-CPU crossover for the closest-match dispatcher
 (``ops/editdistance.py``): times both paths over a range of batch sizes and
-prints one JSON line per size, plus the smallest size where the GPU wins."""
+prints one JSON line per size, plus the smallest size where the GPU wins.
+``--qmin/--qmax`` set the query lengths (65..256 runs the wide tile classes)."""
 
+import argparse
 import json
 import os
 import random
@@ -51,6 +53,10 @@ def cold_start_ms():
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--qmin", type=int, default=4)
+    ap.add_argument("--qmax", type=int, default=24)
+    a = ap.parse_args()
     first, second = cold_start_ms()
     print(json.dumps({"cold_first_call_ms": round(first, 3), "warm_second_call_ms": round(second, 3)}), flush=True)
     rng = random.Random(0)
@@ -60,7 +66,7 @@ def main():
     gpu.ed_closest(words(rng, 1024, 4, 40), words(rng, 8, 4, 20))  # context + arena warm-up
     for n_opts, n_q in ((20, 8), (50, 16), (100, 16), (200, 32), (500, 32), (1000, 64), (2000, 64), (5000, 64), (10000, 128), (20000, 256),
                         (50000, 512), (100000, 1024)):
-        opts, qs = words(rng, n_opts, 4, 40), words(rng, n_q, 4, 24)
+        opts, qs = words(rng, n_opts, 4, 40), words(rng, n_q, a.qmin, a.qmax)
         c = best(lambda: m.closest_batch(opts, qs, th))
         g = best(lambda: gpu.ed_closest(opts, qs))
         pairs = n_opts * n_q

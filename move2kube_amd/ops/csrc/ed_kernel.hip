@@ -9,7 +9,8 @@
 //
 // With substitution cost == insertion + deletion the weighted distance is
 // exactly  |a| + |b| - 2 * LCS(a, b),  so each pair reduces to Hyyro's
-// bit-parallel LCS over a DP column of |query| <= 64 bits.
+// bit-parallel LCS over a DP column of |query| bits: one machine word for
+// queries <= 64 bytes, 2 or 4 u64 words with a carry chain up to 256 bytes.
 //
 // Layout (CDNA4-first; every step below was kept or dropped on rocprofv3
 // numbers, see profiles/r01_ed_kernel*):
@@ -25,6 +26,25 @@
 //    blockIdx.y = tile; its 4 KiB of masks are staged in LDS as two u64
 //    sub-tables, so a character costs two conflict-free ds_read_b64
 //    (banked mod 64 over 32-lane groups) whatever the tile kind.
+//  * Wide tiles (queries of 65..256 bytes).  K128 = 2 queries of <= 128 bytes
+//    (2 u64 column words each), K256 = 1 query of <= 256 bytes (4 words).
+//    Same data movement for both: an 8 KiB LDS table of four 2 KiB sub-tables,
+//    entry c of sub-table h = column word h of the tile, so a character costs
+//    four ds_read_b64 (same banking as above) and four word steps.  Only the
+//    addition links a query's words: one v_add_co_u32 + 3 (K128) or 7 (K256)
+//    v_addc_co_u32 per query and character; the carry out of the top word is
+//    dropped and the classes differ in nothing else.  The tables live in a
+//    region of their own after the 4 KiB narrow ones.  The argmin, the panel
+//    format, the slabs and the host arena are the narrow tiles'.
+//    ISA as compiled (hipcc -O3, gfx950, read from -save-temps), per 32
+//    characters (two options x 16) of the closest kernels: 128 ds_read_b64 and
+//    no ds_read2st64_b64, 256 v_bitop3_b32, 64 v_add_co + 192 v_addc_co (K128)
+//    or 32 + 224 (K256), no compare-and-select carries, no scratch.  VGPRs:
+//    closest K128 56, K256 58; matrix K128 53, K256 57 (K64: 43 / 41), 8
+//    waves/SIMD for all.  The 64-bit __builtin_addcll did not give this (see
+//    lcs_step_wide).  Measured (200k options x 2048 queries, MI355X): 0.203
+//    (K128) and 0.200 ps (K256) of closest-kernel time per option byte x query
+//    x u64 column word against K64's 0.231, see docs/history.md.
 //  * LCS step.  U = V & M; V' = (V + U) | (V & ~M)  (V - U never borrows
 //    because U is a subset of V) = and + add + one v_bitop3_b32 per word.
 //  * Options are sorted by length and cut into panels of 512 (256 threads x 2
@@ -79,11 +99,23 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 //        keep the halves independent, exactly two 16-bit LCS columns)
 //   K32: 4 queries <= 32 bytes, one per 32-bit word
 //   K64: 2 queries <= 64 bytes, one per 64-bit word
-enum { K16 = 0, K32 = 1, K64 = 2 };
+//   K128: 2 queries of 65..128 bytes, two u64 words each  } wide tiles: the add
+//   K256: 1 query of 129..256 bytes, four u64 words       } carries across words
+// NW = column words, NQ = queries, WPQ = u64 words per query (the length of
+// the carry chain), NSUB = 2 KiB LDS sub-tables (one ds_read_b64 each per
+// character), MAXLEN = longest query in bytes.  The host side takes the
+// classes from here too.
+enum { K16 = 0, K32 = 1, K64 = 2, K128 = 3, K256 = 4, NKINDS = 5 };
 template <int KIND> struct TileT;
-template <> struct TileT<K16> { typedef uint32_t W; enum { NW = 4, NQ = 8 }; };
-template <> struct TileT<K32> { typedef uint32_t W; enum { NW = 4, NQ = 4 }; };
-template <> struct TileT<K64> { typedef u64 W; enum { NW = 2, NQ = 2 }; };
+template <> struct TileT<K16> { typedef uint32_t W; enum { NW = 4, NQ = 8, WPQ = 1, NSUB = 2, MAXLEN = 16 }; };
+template <> struct TileT<K32> { typedef uint32_t W; enum { NW = 4, NQ = 4, WPQ = 1, NSUB = 2, MAXLEN = 32 }; };
+template <> struct TileT<K64> { typedef u64 W; enum { NW = 2, NQ = 2, WPQ = 1, NSUB = 2, MAXLEN = 64 }; };
+template <> struct TileT<K128> { typedef u64 W; enum { NW = 4, NQ = 2, WPQ = 2, NSUB = 4, MAXLEN = 128 }; };
+template <> struct TileT<K256> { typedef u64 W; enum { NW = 4, NQ = 1, WPQ = 4, NSUB = 4, MAXLEN = 256 }; };
+// uint4s of one tile's mask tables: 4 KiB narrow, 8 KiB wide.
+template <int KIND> struct TileTable { enum { U4 = TileT<KIND>::NSUB * 128 }; };
+static_assert(TileT<K128>::MAXLEN == 64 * TileT<K128>::WPQ && TileT<K256>::MAXLEN == 64 * TileT<K256>::WPQ,
+              "a wide query fills its u64 words");
 
 // One LCS step of a column word against its match mask.  Hyyro's
 // V' = (V + U) | (V - U) with U = V & M; U's bits are a subset of V's, so
@@ -96,6 +128,11 @@ __device__ __forceinline__ uint32_t or_andn(uint32_t a, uint32_t v, uint32_t m) 
   return __builtin_amdgcn_bitop3_b32(a, v, m, 0xF4);
 }
 
+__device__ __forceinline__ u64 or_andn64(u64 a, u64 v, u64 m) {
+  return ((u64)or_andn((uint32_t)(a >> 32), (uint32_t)(v >> 32), (uint32_t)(m >> 32)) << 32) |
+         or_andn((uint32_t)a, (uint32_t)v, (uint32_t)m);
+}
+
 template <int KIND>
 __device__ __forceinline__ void lcs_step(typename TileT<KIND>::W &V, typename TileT<KIND>::W m) {
   typedef typename TileT<KIND>::W W;
@@ -106,40 +143,75 @@ __device__ __forceinline__ void lcs_step(typename TileT<KIND>::W &V, typename Ti
   } else if constexpr (KIND == K32) {
     V = or_andn(V + U, V, m);
   } else {
-    const W A = V + U;
-    V = ((W)or_andn((uint32_t)(A >> 32), (uint32_t)(V >> 32), (uint32_t)(m >> 32)) << 32) |
-        or_andn((uint32_t)A, (uint32_t)V, (uint32_t)m);
+    V = or_andn64(V + U, V, m);
   }
+}
+
+// The same step on a query's column of WPQ u64 words (wide tiles).  Only the
+// addition links the words: V + U is one WPQ*64-bit sum (a v_add_co_u32 and a
+// run of v_addc_co_u32), the carry out of the top word is dropped, and the
+// V & ~M half stays word-local.  A padding character (every mask 0) has U = 0:
+// no carry, V' = V | V.  Bits above the query's length never match, so a
+// carry that ripples through them is put back by the | V term: they stay set
+// and query_lcs masks them off.
+// The sum is written over 32-bit halves with __builtin_addc: that is what the
+// hardware's carry chain is made of, and the 64-bit __builtin_addcll came out
+// as v_lshl_add_u64 + v_cmp_lt_u64 + v_cndmask carry emulation instead.
+template <int WPQ>
+__device__ __forceinline__ void lcs_step_wide(u64 *V, const u64 *m) {
+  uint32_t A[2 * WPQ];
+  unsigned carry = 0;
+#pragma unroll
+  for (int h = 0; h < 2 * WPQ; h++) {
+    const uint32_t v = (uint32_t)(V[h / 2] >> (32 * (h & 1)));
+    const uint32_t u = v & (uint32_t)(m[h / 2] >> (32 * (h & 1)));
+    A[h] = __builtin_addc(v, u, carry, &carry);
+  }
+#pragma unroll
+  for (int w = 0; w < WPQ; w++) V[w] = or_andn64(((u64)A[2 * w + 1] << 32) | A[2 * w], V[w], m[w]);
 }
 
 // Four coded characters of one option against every word of the tile.
 //
-// LDS layout (4 KiB per tile): two sub-tables of 256 u64 entries, sub-table h
-// at byte 2048*h.  K16/K32: entry c of sub-table h = words 2h (low half) and
-// 2h+1 (high half) of the code's masks; K64: entry c of sub-table h = query h.
-// Each character costs two `ds_read_b64` (bank = (addr/4) mod 64 over 32-lane
+// LDS layout (4 KiB per narrow tile, 8 KiB per wide one): NSUB sub-tables of
+// 256 u64 entries, sub-table h at byte 2048*h.  K16/K32: entry c of sub-table
+// h = words 2h (low half) and 2h+1 (high half) of the code's masks; K64 and
+// the wide tiles: entry c of sub-table h = column word h (K64: query h; K128:
+// query h/2, word h%2; K256: word h of the one query).
+// Each character costs NSUB `ds_read_b64` (bank = (addr/4) mod 64 over 32-lane
 // groups, so the <= 32 most frequent codes never conflict; 2 LDS cycles each).
-// The second address goes through an empty asm so the compiler cannot fuse
-// the pair into `ds_read2st64_b64` - that form banks mod 32 in 16-lane groups
-// and cost 8 cycles + ~7 conflict cycles per instruction in PMC (v5).
+// Every address after the first goes through an empty asm so the compiler
+// cannot fuse a pair into `ds_read2st64_b64` - that form banks mod 32 in
+// 16-lane groups and cost 8 cycles + ~7 conflict cycles per instruction in
+// PMC (v5).
 template <int KIND, bool SCALED>
 __device__ __forceinline__ void step4(uint32_t w, const char *T, typename TileT<KIND>::W (&V)[TileT<KIND>::NW]) {
+  typedef TileT<KIND> TT;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const uint32_t c = (w >> (8 * i)) & 0xffu;
     const uint32_t off = SCALED ? c * 2u : c * 8u;  // byte offset of entry c in a u64 table
-    uint32_t off1 = off + 2048u;
-    __asm__ volatile("" : "+v"(off1));
-    const u64 m0 = *reinterpret_cast<const u64 *>(T + off);
-    const u64 m1 = *reinterpret_cast<const u64 *>(T + off1);
-    if constexpr (KIND == K64) {
-      lcs_step<KIND>(V[0], m0);
-      lcs_step<KIND>(V[1], m1);
+    uint32_t offh[TT::NSUB];
+    u64 m[TT::NSUB];
+    offh[0] = off;
+#pragma unroll
+    for (int h = 1; h < TT::NSUB; h++) {
+      offh[h] = off + 2048u * h;
+      __asm__ volatile("" : "+v"(offh[h]));
+    }
+#pragma unroll
+    for (int h = 0; h < TT::NSUB; h++) m[h] = *reinterpret_cast<const u64 *>(T + offh[h]);
+    if constexpr (TT::WPQ > 1) {
+#pragma unroll
+      for (int q = 0; q < TT::NQ; q++) lcs_step_wide<TT::WPQ>(&V[q * TT::WPQ], &m[q * TT::WPQ]);
+    } else if constexpr (KIND == K64) {
+      lcs_step<KIND>(V[0], m[0]);
+      lcs_step<KIND>(V[1], m[1]);
     } else {
-      lcs_step<KIND>(V[0], (uint32_t)m0);
-      lcs_step<KIND>(V[1], (uint32_t)(m0 >> 32));
-      lcs_step<KIND>(V[2], (uint32_t)m1);
-      lcs_step<KIND>(V[3], (uint32_t)(m1 >> 32));
+      lcs_step<KIND>(V[0], (uint32_t)m[0]);
+      lcs_step<KIND>(V[1], (uint32_t)(m[0] >> 32));
+      lcs_step<KIND>(V[2], (uint32_t)m[1]);
+      lcs_step<KIND>(V[3], (uint32_t)(m[1] >> 32));
     }
   }
 }
@@ -186,16 +258,32 @@ __device__ __forceinline__ int query_lcs(const typename TileT<KIND>::W (&V)[Tile
   } else if constexpr (KIND == K32) {
     const uint32_t mask = len >= 32 ? ~0u : ((1u << len) - 1u);
     return __popc(~V[j] & mask);
-  } else {
+  } else if constexpr (KIND == K64) {
     const u64 mask = len >= 64 ? ~0ULL : ((1ULL << len) - 1ULL);
     return __popcll(~V[j] & mask);
+  } else {
+    // wide: popcounts over the query's words, the length mask on the last one
+    // (an empty slot has len 0: every word is masked to nothing)
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < TileT<KIND>::WPQ; w++) {
+      const int bits = len - 64 * w;
+      const u64 mask = bits >= 64 ? ~0ULL : (bits <= 0 ? 0ULL : ((1ULL << bits) - 1ULL));
+      n += __popcll(~V[j * TileT<KIND>::WPQ + w] & mask);
+    }
+    return n;
   }
 }
 
-// Stage the tile's mask tables (4 KiB) in LDS.
+// Stage the tile's mask tables in LDS.  Narrow (4 KiB) and wide (8 KiB) tables
+// live in regions of their own: a narrow tile is indexed by its tile number
+// (the narrow region comes first), a wide one by its number within the launch,
+// whose `tileM` is the table of the launch's first tile.
+template <int KIND>
 __device__ __forceinline__ void load_tile(const uint4 *__restrict__ tileM, int tile, uint4 *T) {
-  const uint4 *src = tileM + (size_t)tile * 256;
-  for (int i = threadIdx.x; i < 256; i += THREADS) T[i] = src[i];
+  const int row = TileT<KIND>::WPQ > 1 ? (int)blockIdx.y : tile;
+  const uint4 *src = tileM + (size_t)row * TileTable<KIND>::U4;
+  for (int i = threadIdx.x; i < TileTable<KIND>::U4; i += THREADS) T[i] = src[i];
   __syncthreads();
 }
 
@@ -209,9 +297,9 @@ __global__ __launch_bounds__(THREADS) void ed_matrix_kernel(
     const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nA, int nPanels, int tile0,
     int *__restrict__ outT) {
   typedef TileT<KIND> TT;
-  __shared__ uint4 T[256];
+  __shared__ uint4 T[TileTable<KIND>::U4];
   const int tile = tile0 + blockIdx.y;
-  load_tile(tileM, tile, T);
+  load_tile<KIND>(tileM, tile, T);
   int qid[TT::NQ], qlen[TT::NQ];
 #pragma unroll
   for (int j = 0; j < TT::NQ; j++) qid[j] = tileQ[tile * 8 + j], qlen[j] = tileLen[tile * 8 + j];
@@ -237,10 +325,10 @@ __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
     const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
     const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nPanels, int tile0, u64 *__restrict__ best) {
   typedef TileT<KIND> TT;
-  __shared__ uint4 T[256];
+  __shared__ uint4 T[TileTable<KIND>::U4];
   __shared__ u64 red[THREADS / 64][TT::NQ];
   const int tile = tile0 + blockIdx.y;
-  load_tile(tileM, tile, T);
+  load_tile<KIND>(tileM, tile, T);
   int qid[TT::NQ], qlen[TT::NQ];
   u64 key[TT::NQ];
 #pragma unroll
@@ -326,12 +414,33 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
   int nA = 0, nB = 0, nPanels = 0, scaled = 0;
-  int nTiles = 0, kindStart[3] = {0, 0, 0}, kindCount[3] = {0, 0, 0};
+  int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
   int64_t totalU4 = 0;
   size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0;
-  size_t oTileM = 0, oTileQ = 0, oTileLen = 0;
+  size_t oTileM = 0, oTileMWide = 0, oTileQ = 0, oTileLen = 0;  // 4 KiB narrow tables, then 8 KiB wide ones
   size_t h2dBytes = 0, oBest = 0, bytes = 0;
+
+  int narrowTiles() const { return kindCount[K16] + kindCount[K32] + kindCount[K64]; }
+  // Tile kinds are contiguous runs in length order.
+  int kindOf(int tile) const {
+    int kind = 0;
+    for (int k = 1; k < NKINDS; k++)
+      if (kindCount[k] && tile >= kindStart[k]) kind = k;
+    return kind;
+  }
+  // Byte offset of a tile's mask tables, from the start of the staging/device buffer.
+  size_t tileTable(int tile) const {
+    const int narrow = narrowTiles();
+    return tile < narrow ? oTileM + (size_t)4096 * tile : oTileMWide + (size_t)8192 * (tile - narrow);
+  }
 };
+
+#define PER_KIND(F) {TileT<K16>::F, TileT<K32>::F, TileT<K64>::F, TileT<K128>::F, TileT<K256>::F}
+const int kKindMaxLen[NKINDS] = PER_KIND(MAXLEN);
+const int kKindQueries[NKINDS] = PER_KIND(NQ);
+const int kKindWords[NKINDS] = PER_KIND(WPQ);  // u64 words per query
+#undef PER_KIND
+const int kMaxQueryBytes = TileT<NKINDS - 1>::MAXLEN;
 
 struct Arena {
   std::mutex mu;
@@ -413,7 +522,7 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
             Arena &ar, Layout &L) {
   for (int j = 0; j < nB; j++) {
     const int64_t len = offB[j + 1] - offB[j];
-    if (len < 0 || len > 64) return -2;
+    if (len < 0 || len > kMaxQueryBytes) return -2;
   }
   const int nt = host_threads();
   uint8_t code[256];
@@ -453,12 +562,13 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   poff[L.nPanels] = total;
   L.totalU4 = total;
 
-  // Query tiles, by length class: 8 x <=16 B (16-bit halves), 4 x <=32 B, 2 x <=64 B.
+  // Query tiles, by length class: 8 x <=16 B (16-bit halves), 4 x <=32 B, 2 x <=64 B,
+  // then the wide ones: 2 x <=128 B, 1 x <=256 B.
   std::vector<int> qorder(nB);
   {
-    int start[66] = {0};
+    int start[kMaxQueryBytes + 2] = {0};
     for (int j = 0; j < nB; j++) start[(int)(offB[j + 1] - offB[j]) + 1]++;
-    for (int l = 0; l <= 64; l++) start[l + 1] += start[l];
+    for (int l = 0; l <= kMaxQueryBytes; l++) start[l + 1] += start[l];
     for (int j = 0; j < nB; j++) qorder[start[(int)(offB[j + 1] - offB[j])]++] = j;
   }
   std::vector<int> tileQ, tileLen;
@@ -466,8 +576,9 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   for (int r = 0; r < nB; r++) {
     const int j = qorder[r];
     const int len = (int)(offB[j + 1] - offB[j]);
-    const int kind = len <= 16 ? K16 : (len <= 32 ? K32 : K64);
-    const int cap = 8 >> kind;
+    int kind = K16;
+    while (len > kKindMaxLen[kind]) kind++;
+    const int cap = kKindQueries[kind];
     if (kind != kindOfPrev || fill == cap) {
       if (kind != kindOfPrev) L.kindStart[kind] = (int)(tileQ.size() / 8);
       tileQ.insert(tileQ.end(), 8, -1);
@@ -498,7 +609,9 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   L.oTileLen = o;
   o = align256(o + sizeof(int) * (size_t)L.nTiles * 8);
   L.oTileM = o;
-  o = align256(o + (size_t)4096 * L.nTiles);
+  o = align256(o + (size_t)4096 * L.narrowTiles());
+  L.oTileMWide = o;
+  o = align256(o + (size_t)8192 * (L.nTiles - L.narrowTiles()));
   L.h2dBytes = o;
   L.oBest = o;
   o = align256(o + sizeof(u64) * (size_t)nB);
@@ -537,17 +650,12 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   });
   memcpy(h + L.oTileQ, tileQ.data(), sizeof(int) * tileQ.size());
   memcpy(h + L.oTileLen, tileLen.data(), sizeof(int) * tileLen.size());
-  char *tm = h + L.oTileM;
   par_for(L.nTiles, nt, 32, [&](int64_t lo, int64_t hi) {
     for (int64_t t = lo; t < hi; t++) {
-      char *T = tm + (size_t)t * 4096;
-      memset(T, 0, 4096);
-      const int kind = t >= L.kindStart[K64] && L.kindCount[K64] && t < L.kindStart[K64] + L.kindCount[K64]
-                           ? K64
-                           : (t >= L.kindStart[K32] && L.kindCount[K32] && t < L.kindStart[K32] + L.kindCount[K32]
-                                  ? K32
-                                  : K16);
-      for (int slot = 0; slot < (8 >> kind); slot++) {
+      const int kind = L.kindOf((int)t);
+      char *T = h + L.tileTable((int)t);
+      memset(T, 0, kind >= K128 ? 8192 : 4096);
+      for (int slot = 0; slot < kKindQueries[kind]; slot++) {
         const int j = tileQ[t * 8 + slot];
         if (j < 0) continue;
         const int len = tileLen[t * 8 + slot];
@@ -555,7 +663,10 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
           const int c = code[qs[offB[j] + k]];
           // word = the 32-bit column word holding this query; sub-table word/2, half word%2
           u64 *T64 = reinterpret_cast<u64 *>(T);
-          if (kind == K64) {
+          if (kind >= K128) {
+            // sub-table = the u64 column word: the query's first word (slot * words per query) + k / 64
+            T64[(slot * kKindWords[kind] + k / 64) * 256 + c] |= 1ULL << (k % 64);
+          } else if (kind == K64) {
             T64[slot * 256 + c] |= 1ULL << k;
           } else {
             const int word = kind == K32 ? slot : (slot >> 1);
@@ -573,7 +684,9 @@ int grid_x(int nPanels, int tiles) {
   // ~4k workgroups per launch: ~2 rounds of the 256 CUs x 7 resident 256-thread
   // groups, each walking enough panels to amortise staging its 4 KiB tile table
   // and the per-query reductions (16k tiny groups measured 3x slower for K16).
-  // x is a multiple of 8 for the XCD remap.
+  // x is a multiple of 8 for the XCD remap.  The wide tiles keep the target:
+  // a group stages 8 KiB but also does twice the work per panel, and 8 KiB of
+  // LDS still leaves registers, not LDS, as what bounds the resident groups.
   static const int target = getenv("M2K_ED_WGS") ? std::max(1, atoi(getenv("M2K_ED_WGS"))) : 4096;
   int want = (target + tiles - 1) / tiles;
   want = std::max(8, std::min(want, 1024));
@@ -583,19 +696,23 @@ int grid_x(int nPanels, int tiles) {
 }
 
 struct DevPtrs {
+  const char *base;  // the tile tables are addressed through Layout::tileTable
   const uint4 *panels;
   const int64_t *panelOff;
   const int *panelBlocks, *lenSorted, *perm, *tileQ, *tileLen;
-  const uint4 *tileM;
   u64 *best;
 };
 
 DevPtrs dev_ptrs(const Arena &ar, const Layout &L) {
   char *d = ar.dev;
-  return {reinterpret_cast<const uint4 *>(d + L.oPanels), reinterpret_cast<const int64_t *>(d + L.oPanelOff),
-          reinterpret_cast<const int *>(d + L.oPanelBlocks), reinterpret_cast<const int *>(d + L.oLenSorted),
-          reinterpret_cast<const int *>(d + L.oPerm),        reinterpret_cast<const int *>(d + L.oTileQ),
-          reinterpret_cast<const int *>(d + L.oTileLen),     reinterpret_cast<const uint4 *>(d + L.oTileM),
+  return {d,
+          reinterpret_cast<const uint4 *>(d + L.oPanels),
+          reinterpret_cast<const int64_t *>(d + L.oPanelOff),
+          reinterpret_cast<const int *>(d + L.oPanelBlocks),
+          reinterpret_cast<const int *>(d + L.oLenSorted),
+          reinterpret_cast<const int *>(d + L.oPerm),
+          reinterpret_cast<const int *>(d + L.oTileQ),
+          reinterpret_cast<const int *>(d + L.oTileLen),
           reinterpret_cast<u64 *>(d + L.oBest)};
 }
 
@@ -607,12 +724,14 @@ int launch_kind(const Layout &L, const DevPtrs &d, int nA, int *out, hipStream_t
   for (int t = 0; t < count; t += MAX_Y) {
     const int rows = std::min(MAX_Y, count - t);
     const int tile0 = L.kindStart[KIND] + t;
+    // narrow kernels index the narrow region by tile number, wide ones get the table of the slab's first tile
+    const uint4 *tileM = reinterpret_cast<const uint4 *>(d.base + (KIND < K128 ? L.oTileM : L.tileTable(tile0)));
     if (out)
       hipLaunchKernelGGL((ed_matrix_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, d.panels, d.panelOff,
-                         d.panelBlocks, d.lenSorted, d.perm, d.tileM, d.tileQ, d.tileLen, nA, L.nPanels, tile0, out);
+                         d.panelBlocks, d.lenSorted, d.perm, tileM, d.tileQ, d.tileLen, nA, L.nPanels, tile0, out);
     else
       hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, d.panels,
-                         d.panelOff, d.panelBlocks, d.lenSorted, d.perm, d.tileM, d.tileQ, d.tileLen, L.nPanels, tile0,
+                         d.panelOff, d.panelBlocks, d.lenSorted, d.perm, tileM, d.tileQ, d.tileLen, L.nPanels, tile0,
                          d.best);
     if (hipGetLastError() != hipSuccess) return -5;
   }
@@ -624,6 +743,8 @@ int launch_all(const Layout &L, const DevPtrs &d, int nA, int *out, hipStream_t 
   int rc = launch_kind<K16, SCALED>(L, d, nA, out, s);
   if (rc == 0) rc = launch_kind<K32, SCALED>(L, d, nA, out, s);
   if (rc == 0) rc = launch_kind<K64, SCALED>(L, d, nA, out, s);
+  if (rc == 0) rc = launch_kind<K128, SCALED>(L, d, nA, out, s);
+  if (rc == 0) rc = launch_kind<K256, SCALED>(L, d, nA, out, s);
   return rc;
 }
 
@@ -653,8 +774,8 @@ void record_times(Arena &ar, double prep) {
 extern "C" {
 
 // Full distance matrix, query-major: outT[j * nA + i] = dist(opts[i], queries[j]).
-// Strings are packed back to back with (n+1) int64 offsets.  Queries must be <= 64 bytes.
-// Returns 0 on success, negative on error.
+// Strings are packed back to back with (n+1) int64 offsets.  Queries must be <= 256 bytes
+// (-2 otherwise).  Returns 0 on success, negative on error.
 int m2k_ed_matrix(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
                   int32_t *outT) {
   int ndev = 0;

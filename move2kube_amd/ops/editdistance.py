@@ -77,10 +77,12 @@ def _use_gpu(pairs, device, queries):
     if device != "gpu" and pairs < GPU_MIN_PAIRS:
         return False
     gpu = _gpu()
-    fits = all(len(q.encode("utf-8", "surrogateescape") if isinstance(q, str) else q) <= 64 for q in queries)
+    # the limit belongs to the kernel library; one that states none has the single-word kernels' 64
+    limit = getattr(gpu, "MAX_QUERY_BYTES", 64)
+    fits = all(len(q.encode("utf-8", "surrogateescape") if isinstance(q, str) else q) <= limit for q in queries)
     if device == "gpu":
         if not fits:
-            raise gpu.GpuUnavailable("queries longer than 64 bytes are not supported on the GPU path")
+            raise gpu.GpuUnavailable("queries longer than %d bytes are not supported on the GPU path" % limit)
         return True
     if not fits or pairs < GPU_MIN_PAIRS or not gpu.gpu_host():
         return False

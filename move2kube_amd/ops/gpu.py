@@ -24,8 +24,13 @@ class GpuUnavailable(RuntimeError):
     pass
 
 
+# Longest query the kernels take (the widest tile class holds one DP column of
+# 4 x 64 bits); the dispatcher reads the limit from here.
+MAX_QUERY_BYTES = 256
+
+
 class GpuUnsupportedInput(GpuUnavailable):
-    """The kernel cannot take this input (query > 64 bytes, all 256 byte values used)."""
+    """The kernel cannot take this input (query > MAX_QUERY_BYTES, all 256 byte values used)."""
 
 
 _RC_UNSUPPORTED = (-2, -8)
@@ -139,15 +144,15 @@ def _lib_or_raise():
 
 def ed_matrix(options, queries):
     """Distance matrix, shape [len(options), len(queries)] (int32 numpy view of a
-    query-major device result).  Every query must be <= 64 bytes."""
+    query-major device result).  Every query must be <= MAX_QUERY_BYTES."""
     lib = _lib_or_raise()
     na, nb = len(options), len(queries)
     if na == 0 or nb == 0:
         return np.zeros((na, nb), dtype=np.int32)
     a, offa, _ = _pack(options)
     q, offb, qmax = _pack(queries)
-    if qmax > 64:
-        raise GpuUnsupportedInput("queries longer than 64 bytes are not supported on the GPU path")
+    if qmax > MAX_QUERY_BYTES:
+        raise GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % MAX_QUERY_BYTES)
     outT = np.empty((nb, na), dtype=np.int32)
     rc = lib.m2k_ed_matrix(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb,
                            _ptr(outT, ctypes.c_int32))
@@ -171,8 +176,8 @@ def ed_closest(options, queries):
         return idx, dist
     a, offa, _ = _pack(options)
     q, offb, qmax = _pack(queries)
-    if qmax > 64:
-        raise GpuUnsupportedInput("queries longer than 64 bytes are not supported on the GPU path")
+    if qmax > MAX_QUERY_BYTES:
+        raise GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % MAX_QUERY_BYTES)
     rc = lib.m2k_ed_closest(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb,
                             _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
     if rc in _RC_UNSUPPORTED:
