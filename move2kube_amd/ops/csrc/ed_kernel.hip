@@ -23,19 +23,22 @@
 //    the option characters serves several queries: 8 queries <= 16 bytes
 //    (two per 32-bit word, v_pk_add_u16 keeps the halves independent),
 //    4 <= 32 bytes (one per word) or 2 <= 64 bytes (one u64 each).
-//    blockIdx.y = tile; its 4 KiB of masks are staged in LDS as two u64
-//    sub-tables, so a character costs two conflict-free ds_read_b64
-//    (banked mod 64 over 32-lane groups) whatever the tile kind.
+//  * One table scheme for every class (TileDesc).  The query in slot s of a
+//    tile owns column bits [s*MAXLEN, (s+1)*MAXLEN) of the tile's column.  The
+//    masks are staged in LDS as NSUB = NQ*MAXLEN/64 sub-tables of 256 u64
+//    entries (2 KiB each): entry c of sub-table h = bits [64h, 64h+64) of
+//    code c's match mask, so a character costs NSUB conflict-free ds_read_b64
+//    (banked mod 64 over 32-lane groups): two (4 KiB) for the classes up to
+//    64 bytes, four (8 KiB) for the wide ones.  In the staging/device buffer
+//    the tables lie in class order, each class a run of equally sized tables;
+//    a launch gets pointers to its first tile's tables and tileQ/tileLen rows
+//    and blockIdx.y counts tiles from there.
 //  * Wide tiles (queries of 65..256 bytes).  K128 = 2 queries of <= 128 bytes
 //    (2 u64 column words each), K256 = 1 query of <= 256 bytes (4 words).
-//    Same data movement for both: an 8 KiB LDS table of four 2 KiB sub-tables,
-//    entry c of sub-table h = column word h of the tile, so a character costs
-//    four ds_read_b64 (same banking as above) and four word steps.  Only the
-//    addition links a query's words: one v_add_co_u32 + 3 (K128) or 7 (K256)
-//    v_addc_co_u32 per query and character; the carry out of the top word is
-//    dropped and the classes differ in nothing else.  The tables live in a
-//    region of their own after the 4 KiB narrow ones.  The argmin, the panel
-//    format, the slabs and the host arena are the narrow tiles'.
+//    Same data movement for both: four ds_read_b64 and four word steps per
+//    character.  Only the addition links a query's words: one v_add_co_u32 +
+//    3 (K128) or 7 (K256) v_addc_co_u32 per query and character; the carry out
+//    of the top word is dropped and the classes differ in nothing else.
 //    ISA as compiled (hipcc -O3, gfx950, read from -save-temps), per 32
 //    characters (two options x 16) of the closest kernels: 128 ds_read_b64 and
 //    no ds_read2st64_b64, 256 v_bitop3_b32, 64 v_add_co + 192 v_addc_co (K128)
@@ -101,21 +104,41 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 //   K64: 2 queries <= 64 bytes, one per 64-bit word
 //   K128: 2 queries of 65..128 bytes, two u64 words each  } wide tiles: the add
 //   K256: 1 query of 129..256 bytes, four u64 words       } carries across words
-// NW = column words, NQ = queries, WPQ = u64 words per query (the length of
+// A class chooses W (the register word of the column), NQ (queries per tile)
+// and MAXLEN (longest query in bytes); the query in slot s owns column bits
+// [s*MAXLEN, (s+1)*MAXLEN).  Derived: WPQ = u64 words per query (the length of
 // the carry chain), NSUB = 2 KiB LDS sub-tables (one ds_read_b64 each per
-// character), MAXLEN = longest query in bytes.  The host side takes the
-// classes from here too.
+// character), NW = column words, TABLE_BYTES / TABLE_U4 = one tile's mask
+// tables.  The host side takes the classes from here too.
+constexpr int kTableEntries = 256;                            // entries per sub-table: one per byte code
+constexpr int kSubTableBytes = kTableEntries * sizeof(u64);  // 2 KiB
+constexpr int kTileSlots = 8;                                 // slots per tile in tileQ / tileLen
+template <class W_, int NQ_, int MAXLEN_>
+struct TileDesc {
+  typedef W_ W;
+  enum {
+    NQ = NQ_,
+    MAXLEN = MAXLEN_,
+    WPQ = MAXLEN > 64 ? MAXLEN / 64 : 1,
+    NSUB = NQ * MAXLEN / 64,
+    NW = NQ * MAXLEN / (8 * sizeof(W)),
+    TABLE_BYTES = NSUB * kSubTableBytes,
+    TABLE_U4 = TABLE_BYTES / sizeof(uint4)
+  };
+  static_assert(NSUB == 2 || NSUB == 4, "step4 reads 2 or 4 sub-tables per character");
+  static_assert(NQ <= kTileSlots, "a tile's queries fit its tileQ / tileLen row");
+  static_assert(MAXLEN <= 64 || (MAXLEN == 64 * WPQ && sizeof(W) == sizeof(u64)), "a wide query fills its u64 words");
+};
 enum { K16 = 0, K32 = 1, K64 = 2, K128 = 3, K256 = 4, NKINDS = 5 };
 template <int KIND> struct TileT;
-template <> struct TileT<K16> { typedef uint32_t W; enum { NW = 4, NQ = 8, WPQ = 1, NSUB = 2, MAXLEN = 16 }; };
-template <> struct TileT<K32> { typedef uint32_t W; enum { NW = 4, NQ = 4, WPQ = 1, NSUB = 2, MAXLEN = 32 }; };
-template <> struct TileT<K64> { typedef u64 W; enum { NW = 2, NQ = 2, WPQ = 1, NSUB = 2, MAXLEN = 64 }; };
-template <> struct TileT<K128> { typedef u64 W; enum { NW = 4, NQ = 2, WPQ = 2, NSUB = 4, MAXLEN = 128 }; };
-template <> struct TileT<K256> { typedef u64 W; enum { NW = 4, NQ = 1, WPQ = 4, NSUB = 4, MAXLEN = 256 }; };
-// uint4s of one tile's mask tables: 4 KiB narrow, 8 KiB wide.
-template <int KIND> struct TileTable { enum { U4 = TileT<KIND>::NSUB * 128 }; };
-static_assert(TileT<K128>::MAXLEN == 64 * TileT<K128>::WPQ && TileT<K256>::MAXLEN == 64 * TileT<K256>::WPQ,
-              "a wide query fills its u64 words");
+template <> struct TileT<K16> : TileDesc<uint32_t, 8, 16> {};
+template <> struct TileT<K32> : TileDesc<uint32_t, 4, 32> {};
+template <> struct TileT<K64> : TileDesc<u64, 2, 64> {};
+template <> struct TileT<K128> : TileDesc<u64, 2, 128> {};
+template <> struct TileT<K256> : TileDesc<u64, 1, 256> {};
+static_assert(TileT<K16>::MAXLEN < TileT<K32>::MAXLEN && TileT<K32>::MAXLEN < TileT<K64>::MAXLEN &&
+                  TileT<K64>::MAXLEN < TileT<K128>::MAXLEN && TileT<K128>::MAXLEN < TileT<K256>::MAXLEN,
+              "the host picks the first class whose MAXLEN holds the query");
 
 // One LCS step of a column word against its match mask.  Hyyro's
 // V' = (V + U) | (V - U) with U = V & M; U's bits are a subset of V's, so
@@ -173,11 +196,12 @@ __device__ __forceinline__ void lcs_step_wide(u64 *V, const u64 *m) {
 
 // Four coded characters of one option against every word of the tile.
 //
-// LDS layout (4 KiB per narrow tile, 8 KiB per wide one): NSUB sub-tables of
-// 256 u64 entries, sub-table h at byte 2048*h.  K16/K32: entry c of sub-table
-// h = words 2h (low half) and 2h+1 (high half) of the code's masks; K64 and
-// the wide tiles: entry c of sub-table h = column word h (K64: query h; K128:
-// query h/2, word h%2; K256: word h of the one query).
+// LDS layout (TABLE_BYTES per tile): NSUB sub-tables of kTableEntries u64
+// entries, sub-table h at byte kSubTableBytes*h, entry c of sub-table h = bits
+// [64h, 64h+64) of code c's mask over the tile's column.  In register words:
+// K16/K32: words 2h (low half) and 2h+1 (high half); K64 and the wide tiles:
+// column word h (K64: query h; K128: query h/2, word h%2; K256: word h of the
+// one query).
 // Each character costs NSUB `ds_read_b64` (bank = (addr/4) mod 64 over 32-lane
 // groups, so the <= 32 most frequent codes never conflict; 2 LDS cycles each).
 // Every address after the first goes through an empty asm so the compiler
@@ -196,7 +220,7 @@ __device__ __forceinline__ void step4(uint32_t w, const char *T, typename TileT<
     offh[0] = off;
 #pragma unroll
     for (int h = 1; h < TT::NSUB; h++) {
-      offh[h] = off + 2048u * h;
+      offh[h] = off + kSubTableBytes * h;
       __asm__ volatile("" : "+v"(offh[h]));
     }
 #pragma unroll
@@ -275,34 +299,33 @@ __device__ __forceinline__ int query_lcs(const typename TileT<KIND>::W (&V)[Tile
   }
 }
 
-// Stage the tile's mask tables in LDS.  Narrow (4 KiB) and wide (8 KiB) tables
-// live in regions of their own: a narrow tile is indexed by its tile number
-// (the narrow region comes first), a wide one by its number within the launch,
-// whose `tileM` is the table of the launch's first tile.
+// Stage the tile's mask tables in LDS.  `tileM` is the table of the launch's
+// first tile and the launch's tiles are one class, so tile number `tile` of
+// the launch (blockIdx.y) lies `tile` tables further on.
 template <int KIND>
 __device__ __forceinline__ void load_tile(const uint4 *__restrict__ tileM, int tile, uint4 *T) {
-  const int row = TileT<KIND>::WPQ > 1 ? (int)blockIdx.y : tile;
-  const uint4 *src = tileM + (size_t)row * TileTable<KIND>::U4;
-  for (int i = threadIdx.x; i < TileTable<KIND>::U4; i += THREADS) T[i] = src[i];
+  const uint4 *src = tileM + (size_t)tile * TileT<KIND>::TABLE_U4;
+  for (int i = threadIdx.x; i < TileT<KIND>::TABLE_U4; i += THREADS) T[i] = src[i];
   __syncthreads();
 }
 
-}  // namespace
-
-// Tile metadata: tileQ[t][8] = query index (-1 = empty), tileLen[t][8] = its length.
-template <int KIND, bool SCALED>
-__global__ __launch_bounds__(THREADS) void ed_matrix_kernel(
+// What both kernels do: stage the tile's tables, walk this workgroup's panels
+// and, for every real option slot of the lane, call f(o, dist) with the
+// option's original index and dist(j) = its distance to the tile's query j.
+// Tile metadata: tileQ[t][kTileSlots] = query index (-1 = empty), tileLen[t][kTileSlots]
+// = its length, t counted from the launch's first tile like the tables.
+template <int KIND, bool SCALED, class F>
+__device__ __forceinline__ void for_each_option(
     const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
     const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
-    const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nA, int nPanels, int tile0,
-    int *__restrict__ outT) {
+    const int *__restrict__ tileLen, int nPanels, F f) {
   typedef TileT<KIND> TT;
-  __shared__ uint4 T[TileTable<KIND>::U4];
-  const int tile = tile0 + blockIdx.y;
+  __shared__ uint4 T[TT::TABLE_U4];
+  const int tile = blockIdx.y;
   load_tile<KIND>(tileM, tile, T);
-  int qid[TT::NQ], qlen[TT::NQ];
+  int qlen[TT::NQ];
 #pragma unroll
-  for (int j = 0; j < TT::NQ; j++) qid[j] = tileQ[tile * 8 + j], qlen[j] = tileLen[tile * 8 + j];
+  for (int j = 0; j < TT::NQ; j++) qlen[j] = tileLen[tile * kTileSlots + j];
   for (int p = remap_panel(blockIdx.x, gridDim.x); p < nPanels; p += gridDim.x) {
     typename TT::W V[OPT_PER_THREAD][TT::NW];
     panel_lcs<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), V);
@@ -312,44 +335,52 @@ __global__ __launch_bounds__(THREADS) void ed_matrix_kernel(
       const int o = perm[s];
       if (o < 0) continue;
       const int la = lenSorted[s];
-#pragma unroll
-      for (int j = 0; j < TT::NQ; j++)
-        if (qid[j] >= 0) outT[(size_t)qid[j] * nA + o] = la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
+      auto dist = [&](int j) __attribute__((always_inline)) {
+        return la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
+      };
+      f(o, dist);
     }
   }
+}
+
+}  // namespace
+
+template <int KIND, bool SCALED>
+__global__ __launch_bounds__(THREADS) void ed_matrix_kernel(
+    const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
+    const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
+    const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nA, int nPanels, int *__restrict__ outT) {
+  typedef TileT<KIND> TT;
+  const int tile = blockIdx.y;
+  int qid[TT::NQ];
+#pragma unroll
+  for (int j = 0; j < TT::NQ; j++) qid[j] = tileQ[tile * kTileSlots + j];
+  auto store = [&](int o, auto dist) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < TT::NQ; j++)
+      if (qid[j] >= 0) outT[(size_t)qid[j] * nA + o] = dist(j);
+  };
+  for_each_option<KIND, SCALED>(panels, panelOff, panelBlocks, lenSorted, perm, tileM, tileLen, nPanels, store);
 }
 
 template <int KIND, bool SCALED>
 __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
     const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
     const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
-    const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nPanels, int tile0, u64 *__restrict__ best) {
+    const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nPanels, u64 *__restrict__ best) {
   typedef TileT<KIND> TT;
-  __shared__ uint4 T[TileTable<KIND>::U4];
   __shared__ u64 red[THREADS / 64][TT::NQ];
-  const int tile = tile0 + blockIdx.y;
-  load_tile<KIND>(tileM, tile, T);
-  int qid[TT::NQ], qlen[TT::NQ];
   u64 key[TT::NQ];
 #pragma unroll
-  for (int j = 0; j < TT::NQ; j++) qid[j] = tileQ[tile * 8 + j], qlen[j] = tileLen[tile * 8 + j], key[j] = ~0ULL;
-  for (int p = remap_panel(blockIdx.x, gridDim.x); p < nPanels; p += gridDim.x) {
-    typename TT::W V[OPT_PER_THREAD][TT::NW];
-    panel_lcs<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), V);
+  for (int j = 0; j < TT::NQ; j++) key[j] = ~0ULL;
+  auto keep_min = [&](int o, auto dist) __attribute__((always_inline)) {
 #pragma unroll
-    for (int u = 0; u < OPT_PER_THREAD; u++) {
-      const int s = p * SLOTS + u * THREADS + threadIdx.x;
-      const int o = perm[s];
-      if (o < 0) continue;
-      const int la = lenSorted[s];
-#pragma unroll
-      for (int j = 0; j < TT::NQ; j++) {
-        const int d = la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
-        const u64 k = ((u64)(unsigned)d << 32) | (unsigned)o;
-        key[j] = k < key[j] ? k : key[j];
-      }
+    for (int j = 0; j < TT::NQ; j++) {
+      const u64 k = ((u64)(unsigned)dist(j) << 32) | (unsigned)o;
+      key[j] = k < key[j] ? k : key[j];
     }
-  }
+  };
+  for_each_option<KIND, SCALED>(panels, panelOff, panelBlocks, lenSorted, perm, tileM, tileLen, nPanels, keep_min);
   // argmin per query: wave shuffles, then the 4 waves through LDS, one atomic each
 #pragma unroll
   for (int j = 0; j < TT::NQ; j++) {
@@ -363,7 +394,7 @@ __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
   __syncthreads();
   if (threadIdx.x < TT::NQ) {
     const int j = threadIdx.x;
-    const int q = tileQ[tile * 8 + j];  // (not qid[j]: a dynamic index would spill the array)
+    const int q = tileQ[(int)blockIdx.y * kTileSlots + j];  // (not a qid[j] array: a dynamic index would spill it)
     u64 k = red[0][j];
     for (int w = 1; w < THREADS / 64; w++) k = red[w][j] < k ? red[w][j] : k;
     if (q >= 0 && k != ~0ULL) atomicMin(&best[q], k);
@@ -412,35 +443,27 @@ void par_for(int64_t n, int nt, int64_t grain, F f) {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-struct Layout {
-  int nA = 0, nB = 0, nPanels = 0, scaled = 0;
-  int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
-  int64_t totalU4 = 0;
-  size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0;
-  size_t oTileM = 0, oTileMWide = 0, oTileQ = 0, oTileLen = 0;  // 4 KiB narrow tables, then 8 KiB wide ones
-  size_t h2dBytes = 0, oBest = 0, bytes = 0;
-
-  int narrowTiles() const { return kindCount[K16] + kindCount[K32] + kindCount[K64]; }
-  // Tile kinds are contiguous runs in length order.
-  int kindOf(int tile) const {
-    int kind = 0;
-    for (int k = 1; k < NKINDS; k++)
-      if (kindCount[k] && tile >= kindStart[k]) kind = k;
-    return kind;
-  }
-  // Byte offset of a tile's mask tables, from the start of the staging/device buffer.
-  size_t tileTable(int tile) const {
-    const int narrow = narrowTiles();
-    return tile < narrow ? oTileM + (size_t)4096 * tile : oTileMWide + (size_t)8192 * (tile - narrow);
-  }
-};
-
 #define PER_KIND(F) {TileT<K16>::F, TileT<K32>::F, TileT<K64>::F, TileT<K128>::F, TileT<K256>::F}
 const int kKindMaxLen[NKINDS] = PER_KIND(MAXLEN);
 const int kKindQueries[NKINDS] = PER_KIND(NQ);
-const int kKindWords[NKINDS] = PER_KIND(WPQ);  // u64 words per query
+const size_t kKindTableBytes[NKINDS] = PER_KIND(TABLE_BYTES);
 #undef PER_KIND
 const int kMaxQueryBytes = TileT<NKINDS - 1>::MAXLEN;
+
+// Offsets into the staging/device buffer.  Tile kinds are contiguous runs of
+// tiles in length order, and so are their tables.
+struct Layout {
+  int nA = 0, nB = 0, nPanels = 0, scaled = 0;
+  int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
+  size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0, oTileQ = 0, oTileLen = 0;
+  size_t kindTableOff[NKINDS] = {0, 0, 0, 0, 0};  // the tables of the kind's first tile
+  size_t h2dBytes = 0, oBest = 0, bytes = 0;
+
+  // Byte offset of the mask tables of a tile of `kind`.
+  size_t tileTable(int kind, int tile) const {
+    return kindTableOff[kind] + kKindTableBytes[kind] * (size_t)(tile - kindStart[kind]);
+  }
+};
 
 struct Arena {
   std::mutex mu;
@@ -517,53 +540,60 @@ bool build_code_map(const uint8_t *opts, int64_t nOptBytes, const uint8_t *qs, i
   return true;
 }
 
-// Everything up to (not including) the H2D copy.  Returns 0 or an error code.
-int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-            Arena &ar, Layout &L) {
+bool query_lengths_ok(const int64_t *offB, int nB) {
   for (int j = 0; j < nB; j++) {
     const int64_t len = offB[j + 1] - offB[j];
-    if (len < 0 || len > kMaxQueryBytes) return -2;
+    if (len < 0 || len > kMaxQueryBytes) return false;
   }
-  const int nt = host_threads();
-  uint8_t code[256];
-  int nsym = 0;
-  if (!build_code_map(opts, offA[nA], qs, offB[nB], nt, code, &nsym)) return -8;
-  L.nA = nA;
-  L.nB = nB;
-  L.scaled = nsym <= 63;
-  uint8_t stored[256];
-  for (int b = 0; b < 256; b++) stored[b] = L.scaled ? (uint8_t)(code[b] * 4) : code[b];
+  return true;
+}
 
+// Options in length order (stable), cut into panels of SLOTS: blocks[p] =
+// 16-byte blocks of panel p, off[p] = its first uint4 (off[nPanels] = total).
+struct PanelPlan {
+  std::vector<int> order, blocks;
+  std::vector<int64_t> off;
+};
+
+PanelPlan plan_panels(const int64_t *offA, int nA) {
+  PanelPlan P;
   // stable counting sort of the options by length
   int maxLen = 0;
   for (int i = 0; i < nA; i++) maxLen = std::max(maxLen, (int)(offA[i + 1] - offA[i]));
-  std::vector<int> order(nA);
+  P.order.resize(nA);
   if (maxLen <= (1 << 20)) {
     std::vector<int> start(maxLen + 2, 0);
     for (int i = 0; i < nA; i++) start[(int)(offA[i + 1] - offA[i]) + 1]++;
     for (int l = 0; l <= maxLen; l++) start[l + 1] += start[l];
-    for (int i = 0; i < nA; i++) order[start[(int)(offA[i + 1] - offA[i])]++] = i;
+    for (int i = 0; i < nA; i++) P.order[start[(int)(offA[i + 1] - offA[i])]++] = i;
   } else {
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(),
+    std::iota(P.order.begin(), P.order.end(), 0);
+    std::stable_sort(P.order.begin(), P.order.end(),
                      [&](int x, int y) { return (offA[x + 1] - offA[x]) < (offA[y + 1] - offA[y]); });
   }
-  L.nPanels = (nA + SLOTS - 1) / SLOTS;
-  std::vector<int> blocks(L.nPanels);
-  std::vector<int64_t> poff(L.nPanels + 1);
+  const int nPanels = (nA + SLOTS - 1) / SLOTS;
+  P.blocks.resize(nPanels);
+  P.off.resize(nPanels + 1);
   int64_t total = 0;
-  for (int p = 0; p < L.nPanels; p++) {
+  for (int p = 0; p < nPanels; p++) {
     const int last = std::min(nA, (p + 1) * SLOTS) - 1;  // sorted: the panel's longest option
-    const int o = order[last];
-    blocks[p] = (int)((offA[o + 1] - offA[o] + 15) / 16);
-    poff[p] = total;
-    total += (int64_t)blocks[p] * SLOTS;
+    const int o = P.order[last];
+    P.blocks[p] = (int)((offA[o + 1] - offA[o] + 15) / 16);
+    P.off[p] = total;
+    total += (int64_t)P.blocks[p] * SLOTS;
   }
-  poff[L.nPanels] = total;
-  L.totalU4 = total;
+  P.off[nPanels] = total;
+  return P;
+}
 
-  // Query tiles, by length class: 8 x <=16 B (16-bit halves), 4 x <=32 B, 2 x <=64 B,
-  // then the wide ones: 2 x <=128 B, 1 x <=256 B.
+// Query tiles: the queries in length order, each in the first class whose
+// MAXLEN holds it, NQ of them to a tile.  q / len are the tileQ / tileLen rows
+// (kTileSlots per tile); kindStart / kindCount get each class's run of tiles.
+struct TilePlan {
+  std::vector<int> q, len;
+};
+
+TilePlan plan_tiles(const int64_t *offB, int nB, int kindStart[NKINDS], int kindCount[NKINDS]) {
   std::vector<int> qorder(nB);
   {
     int start[kMaxQueryBytes + 2] = {0};
@@ -571,63 +601,57 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
     for (int l = 0; l <= kMaxQueryBytes; l++) start[l + 1] += start[l];
     for (int j = 0; j < nB; j++) qorder[start[(int)(offB[j + 1] - offB[j])]++] = j;
   }
-  std::vector<int> tileQ, tileLen;
+  TilePlan P;
   int kindOfPrev = -1, fill = 0;
   for (int r = 0; r < nB; r++) {
     const int j = qorder[r];
     const int len = (int)(offB[j + 1] - offB[j]);
     int kind = K16;
     while (len > kKindMaxLen[kind]) kind++;
-    const int cap = kKindQueries[kind];
-    if (kind != kindOfPrev || fill == cap) {
-      if (kind != kindOfPrev) L.kindStart[kind] = (int)(tileQ.size() / 8);
-      tileQ.insert(tileQ.end(), 8, -1);
-      tileLen.insert(tileLen.end(), 8, 0);
-      L.kindCount[kind]++;
+    if (kind != kindOfPrev || fill == kKindQueries[kind]) {
+      if (kind != kindOfPrev) kindStart[kind] = (int)(P.q.size() / kTileSlots);
+      P.q.insert(P.q.end(), kTileSlots, -1);
+      P.len.insert(P.len.end(), kTileSlots, 0);
+      kindCount[kind]++;
       kindOfPrev = kind;
       fill = 0;
     }
-    tileQ[tileQ.size() - 8 + fill] = j;
-    tileLen[tileLen.size() - 8 + fill] = len;
+    P.q[P.q.size() - kTileSlots + fill] = j;
+    P.len[P.len.size() - kTileSlots + fill] = len;
     fill++;
   }
-  L.nTiles = (int)(tileQ.size() / 8);
+  return P;
+}
 
+// Offsets of every array in the staging/device buffer; needs L's panel and tile counts.
+void lay_out(Layout &L, int64_t panelU4) {
   size_t o = 0;
-  L.oPanels = o;
-  o = align256(o + sizeof(uint4) * (size_t)std::max<int64_t>(total, 1));
-  L.oPanelOff = o;
-  o = align256(o + sizeof(int64_t) * (size_t)(L.nPanels + 1));
-  L.oPanelBlocks = o;
-  o = align256(o + sizeof(int) * (size_t)L.nPanels);
-  L.oLenSorted = o;
-  o = align256(o + sizeof(int) * (size_t)L.nPanels * SLOTS);
-  L.oPerm = o;
-  o = align256(o + sizeof(int) * (size_t)L.nPanels * SLOTS);
-  L.oTileQ = o;
-  o = align256(o + sizeof(int) * (size_t)L.nTiles * 8);
-  L.oTileLen = o;
-  o = align256(o + sizeof(int) * (size_t)L.nTiles * 8);
-  L.oTileM = o;
-  o = align256(o + (size_t)4096 * L.narrowTiles());
-  L.oTileMWide = o;
-  o = align256(o + (size_t)8192 * (L.nTiles - L.narrowTiles()));
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o = align256(o + bytes);
+    return at;
+  };
+  L.oPanels = take(sizeof(uint4) * (size_t)std::max<int64_t>(panelU4, 1));
+  L.oPanelOff = take(sizeof(int64_t) * (size_t)(L.nPanels + 1));
+  L.oPanelBlocks = take(sizeof(int) * (size_t)L.nPanels);
+  L.oLenSorted = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
+  L.oPerm = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
+  L.oTileQ = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
+  L.oTileLen = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
+  for (int k = 0; k < NKINDS; k++) L.kindTableOff[k] = take(kKindTableBytes[k] * (size_t)L.kindCount[k]);
   L.h2dBytes = o;
-  L.oBest = o;
-  o = align256(o + sizeof(u64) * (size_t)nB);
+  L.oBest = take(sizeof(u64) * (size_t)L.nB);
   L.bytes = o;
-  if (int rc = ar.ensure(L.bytes)) return rc;
+}
 
-  char *h = ar.host;
-  memcpy(h + L.oPanelOff, poff.data(), sizeof(int64_t) * poff.size());
-  memcpy(h + L.oPanelBlocks, blocks.data(), sizeof(int) * blocks.size());
-  int *lenSorted = reinterpret_cast<int *>(h + L.oLenSorted);
-  int *perm = reinterpret_cast<int *>(h + L.oPerm);
-  uint4 *panels = reinterpret_cast<uint4 *>(h + L.oPanels);
-  par_for(L.nPanels, nt, 4, [&](int64_t plo, int64_t phi) {
+// Panels as 16-byte blocks [block][slot] of stored codes, padded with code 0;
+// perm / lenSorted = each slot's original option index (-1 = none) and length.
+void fill_panels(const uint8_t *opts, const int64_t *offA, int nA, const PanelPlan &P, const uint8_t (&stored)[256],
+                 int nt, uint4 *panels, int *perm, int *lenSorted) {
+  par_for((int64_t)P.blocks.size(), nt, 4, [&](int64_t plo, int64_t phi) {
     for (int64_t p = plo; p < phi; p++) {
-      uint8_t *base = reinterpret_cast<uint8_t *>(panels + poff[p]);
-      memset(base, 0, sizeof(uint4) * (size_t)blocks[p] * SLOTS);
+      uint8_t *base = reinterpret_cast<uint8_t *>(panels + P.off[p]);
+      memset(base, 0, sizeof(uint4) * (size_t)P.blocks[p] * SLOTS);
       for (int s = 0; s < SLOTS; s++) {
         const int64_t k = p * SLOTS + s;
         if (k >= nA) {
@@ -635,7 +659,7 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
           lenSorted[k] = 0;
           continue;
         }
-        const int opt = order[k];
+        const int opt = P.order[k];
         const uint8_t *src = opts + offA[opt];
         const int len = (int)(offA[opt + 1] - offA[opt]);
         perm[k] = opt;
@@ -648,35 +672,65 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
       }
     }
   });
-  memcpy(h + L.oTileQ, tileQ.data(), sizeof(int) * tileQ.size());
-  memcpy(h + L.oTileLen, tileLen.data(), sizeof(int) * tileLen.size());
+}
+
+// Mask tables of every tile.  Column-bit convention, the same for every class:
+// the query in slot s owns bits [s*MAXLEN, (s+1)*MAXLEN) of the tile's column,
+// so its byte k is column bit P = s*MAXLEN + k, and a match of code c there is
+// bit P%64 of entry c of sub-table P/64 (step4 and query_lcs read it back as
+// 16-bit halves, 32-bit words or u64 words of that one column).
+void fill_tables(const uint8_t *qs, const int64_t *offB, const uint8_t (&code)[256], const TilePlan &tiles,
+                 const Layout &L, int nt, char *h) {
   par_for(L.nTiles, nt, 32, [&](int64_t lo, int64_t hi) {
-    for (int64_t t = lo; t < hi; t++) {
-      const int kind = L.kindOf((int)t);
-      char *T = h + L.tileTable((int)t);
-      memset(T, 0, kind >= K128 ? 8192 : 4096);
-      for (int slot = 0; slot < kKindQueries[kind]; slot++) {
-        const int j = tileQ[t * 8 + slot];
-        if (j < 0) continue;
-        const int len = tileLen[t * 8 + slot];
-        for (int k = 0; k < len; k++) {
-          const int c = code[qs[offB[j] + k]];
-          // word = the 32-bit column word holding this query; sub-table word/2, half word%2
-          u64 *T64 = reinterpret_cast<u64 *>(T);
-          if (kind >= K128) {
-            // sub-table = the u64 column word: the query's first word (slot * words per query) + k / 64
-            T64[(slot * kKindWords[kind] + k / 64) * 256 + c] |= 1ULL << (k % 64);
-          } else if (kind == K64) {
-            T64[slot * 256 + c] |= 1ULL << k;
-          } else {
-            const int word = kind == K32 ? slot : (slot >> 1);
-            const int bit = kind == K32 ? k : k + 16 * (slot & 1);
-            T64[(word >> 1) * 256 + c] |= (u64)(1u << bit) << (32 * (word & 1));
+    for (int kind = 0; kind < NKINDS; kind++) {  // the part of [lo, hi) that is this kind's run
+      const int64_t end = std::min<int64_t>(hi, L.kindStart[kind] + L.kindCount[kind]);
+      for (int64_t t = std::max<int64_t>(lo, L.kindStart[kind]); t < end; t++) {
+        u64 *T64 = reinterpret_cast<u64 *>(h + L.tileTable(kind, (int)t));
+        memset(T64, 0, kKindTableBytes[kind]);
+        for (int slot = 0; slot < kKindQueries[kind]; slot++) {
+          const int j = tiles.q[t * kTileSlots + slot];
+          if (j < 0) continue;
+          const int len = tiles.len[t * kTileSlots + slot];
+          for (int k = 0; k < len; k++) {
+            const int c = code[qs[offB[j] + k]];
+            const int P = slot * kKindMaxLen[kind] + k;
+            T64[(P / 64) * kTableEntries + c] |= 1ULL << (P % 64);
           }
         }
       }
     }
   });
+}
+
+// Everything up to (not including) the H2D copy.  Returns 0 or an error code.
+int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
+            Arena &ar, Layout &L) {
+  if (!query_lengths_ok(offB, nB)) return -2;
+  const int nt = host_threads();
+  uint8_t code[256];
+  int nsym = 0;
+  if (!build_code_map(opts, offA[nA], qs, offB[nB], nt, code, &nsym)) return -8;
+  L.nA = nA;
+  L.nB = nB;
+  L.scaled = nsym <= 63;
+  uint8_t stored[256];
+  for (int b = 0; b < 256; b++) stored[b] = L.scaled ? (uint8_t)(code[b] * 4) : code[b];
+
+  const PanelPlan panels = plan_panels(offA, nA);
+  L.nPanels = (int)panels.blocks.size();
+  const TilePlan tiles = plan_tiles(offB, nB, L.kindStart, L.kindCount);
+  L.nTiles = (int)(tiles.q.size() / kTileSlots);
+  lay_out(L, panels.off[L.nPanels]);
+  if (int rc = ar.ensure(L.bytes)) return rc;
+
+  char *h = ar.host;
+  memcpy(h + L.oPanelOff, panels.off.data(), sizeof(int64_t) * panels.off.size());
+  memcpy(h + L.oPanelBlocks, panels.blocks.data(), sizeof(int) * panels.blocks.size());
+  fill_panels(opts, offA, nA, panels, stored, nt, reinterpret_cast<uint4 *>(h + L.oPanels),
+              reinterpret_cast<int *>(h + L.oPerm), reinterpret_cast<int *>(h + L.oLenSorted));
+  memcpy(h + L.oTileQ, tiles.q.data(), sizeof(int) * tiles.q.size());
+  memcpy(h + L.oTileLen, tiles.len.data(), sizeof(int) * tiles.len.size());
+  fill_tables(qs, offB, code, tiles, L, nt, h);
   return 0;
 }
 
@@ -695,65 +749,47 @@ int grid_x(int nPanels, int tiles) {
   return x < 1 ? 1 : x;
 }
 
-struct DevPtrs {
-  const char *base;  // the tile tables are addressed through Layout::tileTable
-  const uint4 *panels;
-  const int64_t *panelOff;
-  const int *panelBlocks, *lenSorted, *perm, *tileQ, *tileLen;
-  u64 *best;
-};
-
-DevPtrs dev_ptrs(const Arena &ar, const Layout &L) {
-  char *d = ar.dev;
-  return {d,
-          reinterpret_cast<const uint4 *>(d + L.oPanels),
-          reinterpret_cast<const int64_t *>(d + L.oPanelOff),
-          reinterpret_cast<const int *>(d + L.oPanelBlocks),
-          reinterpret_cast<const int *>(d + L.oLenSorted),
-          reinterpret_cast<const int *>(d + L.oPerm),
-          reinterpret_cast<const int *>(d + L.oTileQ),
-          reinterpret_cast<const int *>(d + L.oTileLen),
-          reinterpret_cast<u64 *>(d + L.oBest)};
+template <class T>
+T *dev_at(const Arena &ar, size_t off) {
+  return reinterpret_cast<T *>(ar.dev + off);
 }
 
+// One class's tiles: the matrix kernels when `out` is set, the closest kernels otherwise.
 template <int KIND, bool SCALED>
-int launch_kind(const Layout &L, const DevPtrs &d, int nA, int *out, hipStream_t s) {
+int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
   const int count = L.kindCount[KIND];
   if (count == 0) return 0;
   const int gx = grid_x(L.nPanels, count);
+  const uint4 *panels = dev_at<uint4>(ar, L.oPanels);
+  const int64_t *panelOff = dev_at<int64_t>(ar, L.oPanelOff);
+  const int *panelBlocks = dev_at<int>(ar, L.oPanelBlocks), *lenSorted = dev_at<int>(ar, L.oLenSorted);
+  const int *perm = dev_at<int>(ar, L.oPerm);
   for (int t = 0; t < count; t += MAX_Y) {
     const int rows = std::min(MAX_Y, count - t);
+    // every launch gets its own first tile's tables and tileQ / tileLen rows
     const int tile0 = L.kindStart[KIND] + t;
-    // narrow kernels index the narrow region by tile number, wide ones get the table of the slab's first tile
-    const uint4 *tileM = reinterpret_cast<const uint4 *>(d.base + (KIND < K128 ? L.oTileM : L.tileTable(tile0)));
+    const uint4 *tileM = dev_at<uint4>(ar, L.tileTable(KIND, tile0));
+    const int *tileQ = dev_at<int>(ar, L.oTileQ) + (size_t)tile0 * kTileSlots;
+    const int *tileLen = dev_at<int>(ar, L.oTileLen) + (size_t)tile0 * kTileSlots;
     if (out)
-      hipLaunchKernelGGL((ed_matrix_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, d.panels, d.panelOff,
-                         d.panelBlocks, d.lenSorted, d.perm, tileM, d.tileQ, d.tileLen, nA, L.nPanels, tile0, out);
+      hipLaunchKernelGGL((ed_matrix_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
+                         panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nA, L.nPanels, out);
     else
-      hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, d.panels,
-                         d.panelOff, d.panelBlocks, d.lenSorted, d.perm, tileM, d.tileQ, d.tileLen, L.nPanels, tile0,
-                         d.best);
+      hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
+                         panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nPanels, dev_at<u64>(ar, L.oBest));
     if (hipGetLastError() != hipSuccess) return -5;
   }
   return 0;
 }
 
 template <bool SCALED>
-int launch_all(const Layout &L, const DevPtrs &d, int nA, int *out, hipStream_t s) {
-  int rc = launch_kind<K16, SCALED>(L, d, nA, out, s);
-  if (rc == 0) rc = launch_kind<K32, SCALED>(L, d, nA, out, s);
-  if (rc == 0) rc = launch_kind<K64, SCALED>(L, d, nA, out, s);
-  if (rc == 0) rc = launch_kind<K128, SCALED>(L, d, nA, out, s);
-  if (rc == 0) rc = launch_kind<K256, SCALED>(L, d, nA, out, s);
+int launch_all(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
+  int rc = launch_kind<K16, SCALED>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K32, SCALED>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K64, SCALED>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K128, SCALED>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K256, SCALED>(L, ar, out, s);
   return rc;
-}
-
-int launch_matrix(const Layout &L, const DevPtrs &d, int nA, int *out, hipStream_t s) {
-  return L.scaled ? launch_all<true>(L, d, nA, out, s) : launch_all<false>(L, d, nA, out, s);
-}
-
-int launch_closest(const Layout &L, const DevPtrs &d, hipStream_t s) {
-  return L.scaled ? launch_all<true>(L, d, 0, nullptr, s) : launch_all<false>(L, d, 0, nullptr, s);
 }
 
 void record_times(Arena &ar, double prep) {
@@ -769,48 +805,24 @@ void record_times(Arena &ar, double prep) {
     fprintf(stderr, "[m2k_ed] prep %.3f ms  h2d %.3f ms  kernel %.3f ms  d2h %.3f ms\n", prep, a, b, c);
 }
 
-}  // namespace
-
-extern "C" {
-
-// Full distance matrix, query-major: outT[j * nA + i] = dist(opts[i], queries[j]).
-// Strings are packed back to back with (n+1) int64 offsets.  Queries must be <= 256 bytes
-// (-2 otherwise).  Returns 0 on success, negative on error.
-int m2k_ed_matrix(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-                  int32_t *outT) {
+// One request: the distance matrix into outT when it is set, the closest
+// option per query into bestIdx / bestDist otherwise.
+//   step                                 returns
+//   no device                            -1
+//   nothing to compute                   0 (closest without options: -1 / -1 per query)
+//   prepare                              -2 query too long, -8 no free byte code, -4 arena
+//   matrix: device output buffer         -4
+//   H2D copy                             -7, at once (no sync)
+//   closest: memset of `best`            -4, at once (no sync)
+//   a kernel launch                      -5  } later launches and the D2H copy are
+//   D2H copy                             -7  } skipped, the stream is synchronised
+//   stream synchronise                   -6 (when nothing failed before)
+// Timings are recorded on success only.
+int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
+        int32_t *outT, int32_t *bestIdx, int32_t *bestDist) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
-  if (nA <= 0 || nB <= 0) return 0;
-  Arena &ar = arena();
-  std::lock_guard<std::mutex> lock(ar.mu);
-  const double t0 = now_ms();
-  Layout L;
-  int rc = prepare(opts, offA, nA, qs, offB, nB, ar, L);
-  if (rc) return rc;
-  if ((rc = ar.ensure_out(sizeof(int) * (size_t)nA * nB))) return rc;
-  const double prep = now_ms() - t0;
-  const DevPtrs d = dev_ptrs(ar, L);
-  hipStream_t s = ar.stream;
-  (void)hipEventRecord(ar.ev[0], s);
-  if (hipMemcpyAsync(ar.dev, ar.host, L.h2dBytes, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
-  (void)hipEventRecord(ar.ev[1], s);
-  rc = launch_matrix(L, d, nA, ar.out, s);
-  (void)hipEventRecord(ar.ev[2], s);
-  if (rc == 0 && hipMemcpyAsync(outT, ar.out, sizeof(int) * (size_t)nA * nB, hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = -7;
-  (void)hipEventRecord(ar.ev[3], s);
-  if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = -6;
-  if (rc == 0) record_times(ar, prep);
-  return rc;
-}
-
-// Closest option per query: bestIdx[j] = first i minimising dist(opts[i], queries[j]),
-// bestDist[j] = that distance (-1/-1 when there are no options).
-int m2k_ed_closest(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-                   int32_t *bestIdx, int32_t *bestDist) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
-  if (nB <= 0) return 0;
+  if (nB <= 0 || (outT && nA <= 0)) return 0;
   if (nA <= 0) {
     for (int j = 0; j < nB; j++) bestIdx[j] = -1, bestDist[j] = -1;
     return 0;
@@ -821,27 +833,51 @@ int m2k_ed_closest(const uint8_t *opts, const int64_t *offA, int nA, const uint8
   Layout L;
   int rc = prepare(opts, offA, nA, qs, offB, nB, ar, L);
   if (rc) return rc;
+  if (outT && (rc = ar.ensure_out(sizeof(int) * (size_t)nA * nB))) return rc;
   const double prep = now_ms() - t0;
-  const DevPtrs d = dev_ptrs(ar, L);
+  u64 *best = dev_at<u64>(ar, L.oBest), *hBest = reinterpret_cast<u64 *>(ar.host + L.oBest);
   hipStream_t s = ar.stream;
   (void)hipEventRecord(ar.ev[0], s);
   if (hipMemcpyAsync(ar.dev, ar.host, L.h2dBytes, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
-  if (hipMemsetAsync(d.best, 0xff, sizeof(u64) * nB, s) != hipSuccess) return -4;
+  if (!outT && hipMemsetAsync(best, 0xff, sizeof(u64) * nB, s) != hipSuccess) return -4;
   (void)hipEventRecord(ar.ev[1], s);
-  rc = launch_closest(L, d, s);
+  int *out = outT ? ar.out : nullptr;
+  rc = L.scaled ? launch_all<true>(L, ar, out, s) : launch_all<false>(L, ar, out, s);
   (void)hipEventRecord(ar.ev[2], s);
-  u64 *hBest = reinterpret_cast<u64 *>(ar.host + L.oBest);
-  if (rc == 0 && hipMemcpyAsync(hBest, d.best, sizeof(u64) * nB, hipMemcpyDeviceToHost, s) != hipSuccess) rc = -7;
+  if (rc == 0) {
+    const hipError_t e = outT ? hipMemcpyAsync(outT, out, sizeof(int) * (size_t)nA * nB, hipMemcpyDeviceToHost, s)
+                              : hipMemcpyAsync(hBest, best, sizeof(u64) * nB, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) rc = -7;
+  }
   (void)hipEventRecord(ar.ev[3], s);
   if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = -6;
-  if (rc == 0) {
+  if (rc) return rc;
+  if (!outT)
     for (int j = 0; j < nB; j++) {
       bestIdx[j] = (int32_t)(hBest[j] & 0xffffffffULL);
       bestDist[j] = (int32_t)(hBest[j] >> 32);
     }
-    record_times(ar, prep);
-  }
-  return rc;
+  record_times(ar, prep);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Full distance matrix, query-major: outT[j * nA + i] = dist(opts[i], queries[j]).
+// Strings are packed back to back with (n+1) int64 offsets.  Queries must be <= 256 bytes
+// (-2 otherwise).  Returns 0 on success, negative on error.
+int m2k_ed_matrix(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
+                  int32_t *outT) {
+  return run(opts, offA, nA, qs, offB, nB, outT, nullptr, nullptr);
+}
+
+// Closest option per query: bestIdx[j] = first i minimising dist(opts[i], queries[j]),
+// bestDist[j] = that distance (-1/-1 when there are no options).
+int m2k_ed_closest(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
+                   int32_t *bestIdx, int32_t *bestDist) {
+  return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist);
 }
 
 // prep / H2D / kernel / D2H milliseconds of the last successful call

@@ -62,13 +62,41 @@ def test_ed_closest_matches_cpu_with_ties():
 
 
 def test_ed_closest_many_query_slabs():
-    # more than 65535 queries exercises the gridDim.y slabbing
+    # more than 65535 queries; their 8,750 tiles (8 queries of <= 16 bytes each)
+    # still fit one gridDim.y slab, see test_launch_past_first_tile_of_class
     rng = random.Random(5)
     opts = _rand_strings(rng, 64, 1, 12)
     qs = _rand_strings(rng, 70000, 0, 10)
     gi, gd = gpu.ed_closest(opts, qs)
     ci, cd = native.module().closest_batch(opts, qs, 8)
     assert np.array_equal(gi, ci) and np.array_equal(gd, cd)
+
+
+def test_launch_past_first_tile_of_class():
+    """More than 65,535 tiles of one class, so a second launch (gridDim.y slab)
+    starts past its class's first tile.  2 x 65,536 + 3 queries of 33..64 bytes
+    make 65,538 two-query tiles: one full slab and a 3-tile one whose last tile
+    is half filled.  4 shorter queries keep that class from starting at tile 0,
+    and 4 longer ones put the wide tables behind the multi-slab region."""
+    rng = random.Random(13)
+    alphabet = "abcdefghij_-0123"
+    pool = "".join(rng.choice(alphabet) for _ in range(1 << 16))
+
+    def cut(n, lo, hi):   # slices of one random string: cheap to build
+        out = []
+        for _ in range(n):
+            at = rng.randrange(len(pool) - hi)
+            out.append(pool[at:at + rng.randint(lo, hi)])
+        return out
+
+    opts = _rand_strings(rng, 8, 1, 12)
+    qs = cut(4, 0, 16) + cut(2 * 65536 + 3, 33, 64) + cut(3, 65, 128) + cut(1, 200, 200)
+    rng.shuffle(qs)
+    gi, gd = gpu.ed_closest(opts, qs)
+    ci, cd = native.module().closest_batch(opts, qs, 8)
+    assert np.array_equal(gi, ci) and np.array_equal(gd, cd)
+    want = native.module().edit_distance_batch(opts, qs, 1, 1, 2, 8)
+    assert np.array_equal(gpu.ed_matrix(opts, qs), want)
 
 
 def test_dispatch_uses_gpu_for_large_batches(monkeypatch):
