@@ -19,9 +19,69 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from move2kube_amd.ops import gpu, native  # noqa: E402
 
 
-def words(rng, n, lo, hi):
-    alpha = "abcdefghijklmnopqrstuvwxyz_-0123456789"
+def words(rng, n, lo, hi, alpha="abcdefghijklmnopqrstuvwxyz_-0123456789"):
     return ["".join(rng.choice(alpha) for _ in range(rng.randint(lo, hi))) for _ in range(n)]
+
+
+def raw_names(rng, names):
+    """Names as a caller has them: first letter upper case and about one
+    separator per 8 characters."""
+    out = []
+    for s in names:
+        cs = list(s[:1].upper() + s[1:])
+        for at in sorted((rng.randrange(len(cs) + 1) for _ in range((len(cs) + 7) // 8)), reverse=True):
+            cs.insert(at, rng.choice("-_. /"))
+        out.append("".join(cs))
+    return out
+
+
+def panel_blocks(names):
+    """16-byte blocks the panels of these options take: 512 options per panel in
+    length order, every slot as long as the panel's longest."""
+    lens = sorted(len(s) for s in names)
+    return sum((lens[min(len(lens), at + 512) - 1] + 15) // 16 * 512 for at in range(0, len(lens), 512))
+
+
+def bench_raw(a, res):
+    """Two routes from raw names to the closest option, in one process:
+    (a) normalise in Python, then ``ed_closest``; (b) ``ed_closest_normalized``."""
+    from move2kube_amd.ops.editdistance import normalize_alnum_lower
+    rng = random.Random(0)
+    alnum = "abcdefghijklmnopqrstuvwxyz0123456789"
+    opts = raw_names(rng, words(rng, a.options, 4, 40, alnum))
+    qs = raw_names(rng, words(rng, a.queries, min(a.qmin, a.qmax), a.qmax, alnum))
+    res.update(raw=True, queries=len(qs), option_bytes=sum(len(o) for o in opts))
+    gpu.ed_closest(opts[:1024], [normalize_alnum_lower(q) for q in qs[:8]])  # warm-up / context creation
+    gpu.ed_closest_normalized(opts[:1024], qs[:8])
+    ta, tn, tb, ka, kb = [], [], [], [], []
+    for _ in range(a.reps):   # the routes alternate
+        t0 = time.perf_counter()
+        no, nq = [normalize_alnum_lower(o) for o in opts], [normalize_alnum_lower(q) for q in qs]
+        t1 = time.perf_counter()
+        ra = gpu.ed_closest(no, nq)
+        t2 = time.perf_counter()
+        ka.append(gpu.last_timings())
+        t3 = time.perf_counter()
+        rb = gpu.ed_closest_normalized(opts, qs)
+        t4 = time.perf_counter()
+        kb.append(gpu.last_timings())
+        tn.append(t1 - t0)
+        ta.append(t2 - t1)
+        tb.append(t4 - t3)
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    res["routes_agree"] = bool((ra[0] == rb[0]).all() and (ra[1] == rb[1]).all())
+    res["a_python_normalise_s"] = med(tn)
+    res["a_gpu_closest_s"] = med(ta)
+    res["a_end_to_end_s"] = med([x + y for x, y in zip(tn, ta)])
+    res["b_end_to_end_s"] = med(tb)
+    for key in ("prep_ms", "h2d_ms", "fill_ms", "kernel_ms", "d2h_ms"):
+        res["a_" + key] = med([k[key] for k in ka])
+        res["b_" + key] = med([k[key] for k in kb])
+    res["panel_blocks_raw"] = panel_blocks(opts)
+    res["panel_blocks_normalised"] = panel_blocks(no)
+    res["arch"] = gpu.device_arch()
+    if not res["routes_agree"]:
+        raise SystemExit("the two routes disagree: " + json.dumps(res))
 
 
 def main():
@@ -33,9 +93,19 @@ def main():
     ap.add_argument("--qmax", type=int, default=64, help="longest query (buildpack names are mostly <= 32)")
     ap.add_argument("--qmin", type=int, default=4, help="shortest query")
     ap.add_argument("--lib", default=None, help="kernel library to load instead of the in-tree one")
+    ap.add_argument("--raw", action="store_true",
+                    help="names with separators and mixed case: Python normalisation + ed_closest against "
+                         "ed_closest_normalized (medians over --reps, the routes checked against each other)")
     a = ap.parse_args()
     if a.lib:
         gpu.LIB_PATH = os.path.abspath(a.lib)
+    if a.raw:
+        if not gpu.available():
+            raise SystemExit("--raw needs the GPU")
+        res = {"options": a.options, "qmin": min(a.qmin, a.qmax), "qmax": a.qmax, "reps": a.reps}
+        bench_raw(a, res)
+        print(json.dumps(res), flush=True)
+        return
     rng = random.Random(0)
     opts = words(rng, a.options, 4, 40)
     qs = words(rng, a.queries, min(a.qmin, a.qmax), a.qmax)

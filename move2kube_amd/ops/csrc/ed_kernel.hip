@@ -401,13 +401,109 @@ __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
   }
 }
 
+// Panel fill on the device (the normalising mode): raw option bytes in, the
+// panels as [block][slot] 16-byte blocks of stored codes and lenSorted out,
+// under a 256-entry byte map built by the host.  Entry 0 = drop the byte, any
+// other entry = the stored code (code*4: this mode always runs the SCALED
+// kernels); bytes that normalise to the same symbol share an entry, so what
+// the normalisation is lies in the map and not in this code.
+//  * Work split.  One lane per panel slot: SLOTS / THREADS workgroups per
+//    panel, grid x = nPanels * SLOTS / THREADS.  Lane s of panel p fills slot
+//    p*SLOTS + s from option perm[slot] (raw bytes offA[o] .. offA[o+1]).
+//  * Byte map.  Staged in LDS once per workgroup by one coalesced dword load
+//    of 64 lanes; a byte costs one ds_read_u8.
+//  * Loads.  Aligned global_load_dwordx4 from the 16-byte block that holds the
+//    option's first byte to the one that holds its last; bytes before the head
+//    and after the tail are masked by index.  `raw` is 256-byte aligned and
+//    its region a multiple of 256 bytes, so no lane reads outside it.  Lanes
+//    of one panel have similar raw lengths (the options are sorted by it), so
+//    the loop is balanced; their addresses are scattered over the raw region.
+//  * Registers.  Kept codes are shifted into a word, full words into a 4-word
+//    shift register (x <- y <- z <- w <- word): after four pushes the block is
+//    in memory order without a dynamically indexed register array.
+//  * Stores.  Every block is one uint4 to panels[panelOff[p] + b*SLOTS + s]:
+//    consecutive lanes write consecutive 16 bytes.  After the last byte the
+//    partial block goes out zero-padded, then zero blocks up to
+//    panelBlocks[p]: the arena is reused between requests and nothing else
+//    clears the panels, and code 0 leaves every column unchanged.  The host
+//    plans panelBlocks from raw lengths, an upper bound on what a lane keeps.
+//  * An empty slot (perm < 0) writes zero blocks and length 0.
+// As compiled (hipcc -O3, gfx950, read from -save-temps): 22 VGPRs, 25 SGPRs,
+// 256 bytes of LDS, no scratch; per 16 raw bytes one global_load_dwordx4 and 16
+// ds_read_u8; every panel store is a global_store_dwordx4 (the only
+// global_store_dword is lenSorted).  The 20 matcher kernels keep their VGPR,
+// SGPR and LDS figures and stay without scratch.
+__global__ __launch_bounds__(THREADS) void ed_fill_panels_kernel(
+    const uint4 *__restrict__ raw, const int64_t *__restrict__ offA, const int *__restrict__ perm,
+    const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks, const uint32_t *__restrict__ byteMap,
+    uint4 *__restrict__ panels, int *__restrict__ lenSorted) {
+  __shared__ uint32_t mapWords[256 / sizeof(uint32_t)];
+  if (threadIdx.x < 256 / sizeof(uint32_t)) mapWords[threadIdx.x] = byteMap[threadIdx.x];
+  __syncthreads();
+  const uint8_t *map = reinterpret_cast<const uint8_t *>(mapWords);
+
+  const int p = blockIdx.x / (SLOTS / THREADS);
+  const int s = (blockIdx.x % (SLOTS / THREADS)) * THREADS + threadIdx.x;
+  const int slot = p * SLOTS + s;
+  const int blocks = panelBlocks[p];
+  uint4 *dst = panels + panelOff[p] + s;
+  const int o = perm[slot];
+
+  uint4 blk = make_uint4(0, 0, 0, 0);
+  uint32_t word = 0;
+  int kept = 0;  // codes kept so far: byte kept%4 of word kept/4%4 of block kept/16 is next
+  auto push_word = [&]() __attribute__((always_inline)) {
+    blk.x = blk.y;
+    blk.y = blk.z;
+    blk.z = blk.w;
+    blk.w = word;
+    word = 0;
+  };
+  auto store_block = [&](int b) __attribute__((always_inline)) {
+    if (b < blocks) dst[(size_t)b * SLOTS] = blk;
+  };
+  if (o >= 0) {
+    const int64_t beg = offA[o], end = offA[o + 1];
+    const int64_t first = beg >> 4;  // the option's first 16-byte block of `raw`
+    const int lo = (int)(beg - (first << 4)), hi = (int)(end - (first << 4));
+    const uint4 *src = raw + first;
+    for (int at = 0; at < hi; at += 16) {  // nothing is loaded for an empty option
+      const uint4 q = *src++;
+      const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const uint32_t c = map[(w4[i / 4] >> (8 * (i % 4))) & 0xffu];
+        if (at + i >= lo && at + i < hi && c != 0) {
+          word |= c << (8 * (kept & 3));
+          kept++;
+          if ((kept & 3) == 0) {
+            push_word();
+            if ((kept & 15) == 0) store_block(kept / 16 - 1);
+          }
+        }
+      }
+    }
+  }
+  int b = kept / 16;
+  if (kept & 15) {  // the partial block: its words so far, the partial word, zero words
+    for (int w = (kept & 15) / 4; w < 4; w++) push_word();
+    store_block(b++);
+  }
+  // (the loop vectoriser would pair these and split every block into four dword stores)
+#pragma clang loop vectorize(disable) interleave(disable)
+  for (; b < blocks; b++) dst[(size_t)b * SLOTS] = make_uint4(0, 0, 0, 0);
+  lenSorted[slot] = kept;
+}
+
 // ---------------------------------------------------------------------------
 // Host side.  One request = code map + length sort + panel fill, written
 // straight into a pinned staging buffer that is laid out exactly like the
 // device buffer, then ONE async H2D copy, the kernels and the D2H of the
 // results on one stream.  Staging/device buffers and the stream live in a
 // grow-only per-process arena (no hipMalloc/hipFree/hipHostMalloc per call;
-// hipFree would also serialise the device).  The fill runs on host threads.
+// hipFree would also serialise the device).  The fill runs on host threads;
+// in a normalising mode (raw names in, see prepare_norm) the raw option bytes
+// are copied instead and ed_fill_panels_kernel fills the panels on the device.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -457,6 +553,7 @@ struct Layout {
   int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
   size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0, oTileQ = 0, oTileLen = 0;
   size_t kindTableOff[NKINDS] = {0, 0, 0, 0, 0};  // the tables of the kind's first tile
+  size_t oRaw = 0, oOffA = 0, oByteMap = 0;       // device fill only: its input
   size_t h2dBytes = 0, oBest = 0, bytes = 0;
 
   // Byte offset of the mask tables of a tile of `kind`.
@@ -473,8 +570,8 @@ struct Arena {
   int *out = nullptr;  // ed_matrix output
   size_t outCap = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  double last[4] = {0, 0, 0, 0};  // prep, h2d, kernel, d2h (ms)
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  double last[5] = {0, 0, 0, 0, 0};  // prep, h2d, kernel, d2h, fill (ms)
 
   int ensure(size_t bytes) {
     if (!stream) {
@@ -513,8 +610,8 @@ Arena &arena() {
 
 // Dense codes ranked by option-byte frequency; 0 is reserved for padding.
 // Returns false when all 256 byte values occur (no free code for padding).
-bool build_code_map(const uint8_t *opts, int64_t nOptBytes, const uint8_t *qs, int64_t nQBytes, int nt,
-                    uint8_t code[256], int *nsym) {
+// The counting pass: freq[b] = how often byte b occurs in the options.
+void count_bytes(const uint8_t *opts, int64_t nOptBytes, int nt, int64_t freq[256]) {
   std::vector<std::array<int64_t, 256>> part(std::max(1, nt));
   for (auto &p : part) p.fill(0);
   std::atomic<int> slot{0};
@@ -522,10 +619,15 @@ bool build_code_map(const uint8_t *opts, int64_t nOptBytes, const uint8_t *qs, i
     auto &f = part[slot.fetch_add(1)];
     for (int64_t i = lo; i < hi; i++) f[opts[i]]++;
   });
-  int64_t freq[256] = {0};
-  bool seen[256] = {false};
+  std::fill(freq, freq + 256, 0);
   for (auto &p : part)
     for (int b = 0; b < 256; b++) freq[b] += p[b];
+}
+
+// The ranking: a code for every symbol that occurs in the options (freq > 0)
+// or the queries, most frequent option symbol first.
+bool rank_codes(const int64_t freq[256], const uint8_t *qs, int64_t nQBytes, uint8_t code[256], int *nsym) {
+  bool seen[256] = {false};
   for (int b = 0; b < 256; b++) seen[b] = freq[b] > 0;
   for (int64_t i = 0; i < nQBytes; i++) seen[qs[i]] = true;
   int order[256];
@@ -538,6 +640,28 @@ bool build_code_map(const uint8_t *opts, int64_t nOptBytes, const uint8_t *qs, i
   for (int i = 0; i < n; i++) code[order[i]] = (uint8_t)(i + 1);
   *nsym = n;
   return true;
+}
+
+bool build_code_map(const uint8_t *opts, int64_t nOptBytes, const uint8_t *qs, int64_t nQBytes, int nt,
+                    uint8_t code[256], int *nsym) {
+  int64_t freq[256];
+  count_bytes(opts, nOptBytes, nt, freq);
+  return rank_codes(freq, qs, nQBytes, code, nsym);
+}
+
+// Normalising modes of run(): what a raw byte becomes before it is matched.
+// A mode is a 256-entry table, 0 = the byte is dropped, anything else = the
+// symbol it stands for.  ALNUM_LOWER is the matcher's caller's
+// lower(strip([^a-zA-Z0-9]+)) on UTF-8 bytes: every byte of a non-ASCII rune
+// is >= 0x80 and goes with the separators, so no rune is ever decoded.
+enum { MODE_NONE = 0, MODE_ALNUM_LOWER = 1 };
+
+void symbol_table(int mode, uint8_t sym[256]) {
+  memset(sym, 0, 256);
+  if (mode == MODE_ALNUM_LOWER) {
+    for (int b = '0'; b <= '9'; b++) sym[b] = (uint8_t)b;
+    for (int b = 'a'; b <= 'z'; b++) sym[b] = sym[b - 'a' + 'A'] = (uint8_t)b;
+  }
 }
 
 bool query_lengths_ok(const int64_t *offB, int nB) {
@@ -624,22 +748,39 @@ TilePlan plan_tiles(const int64_t *offB, int nB, int kindStart[NKINDS], int kind
 }
 
 // Offsets of every array in the staging/device buffer; needs L's panel and tile counts.
-void lay_out(Layout &L, int64_t panelU4) {
+// rawBytes < 0: the host fills the panels and everything up to the tables is
+// copied.  rawBytes >= 0: the device fills them from the raw option bytes, so
+// the copied range ends with the fill kernel's input (option offsets, byte
+// map, raw bytes; every region 256-byte aligned and a multiple of 256 bytes)
+// and the panels and lenSorted lie behind it.
+void lay_out(Layout &L, int64_t panelU4, int64_t rawBytes = -1) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
     o = align256(o + bytes);
     return at;
   };
-  L.oPanels = take(sizeof(uint4) * (size_t)std::max<int64_t>(panelU4, 1));
+  const bool deviceFill = rawBytes >= 0;
+  const size_t panelBytes = sizeof(uint4) * (size_t)std::max<int64_t>(panelU4, 1);
+  const size_t lenBytes = sizeof(int) * (size_t)L.nPanels * SLOTS;
+  if (!deviceFill) L.oPanels = take(panelBytes);
   L.oPanelOff = take(sizeof(int64_t) * (size_t)(L.nPanels + 1));
   L.oPanelBlocks = take(sizeof(int) * (size_t)L.nPanels);
-  L.oLenSorted = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
+  if (!deviceFill) L.oLenSorted = take(lenBytes);
   L.oPerm = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
   L.oTileQ = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
   L.oTileLen = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
   for (int k = 0; k < NKINDS; k++) L.kindTableOff[k] = take(kKindTableBytes[k] * (size_t)L.kindCount[k]);
+  if (deviceFill) {
+    L.oOffA = take(sizeof(int64_t) * (size_t)(L.nA + 1));
+    L.oByteMap = take(256);
+    L.oRaw = take((size_t)rawBytes);
+  }
   L.h2dBytes = o;
+  if (deviceFill) {
+    L.oPanels = take(panelBytes);
+    L.oLenSorted = take(lenBytes);
+  }
   L.oBest = take(sizeof(u64) * (size_t)L.nB);
   L.bytes = o;
 }
@@ -734,6 +875,61 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   return 0;
 }
 
+// prepare() of a normalising mode: the options go to the device as they are
+// and ed_fill_panels_kernel does their per-byte work.  The host normalises the
+// queries (few, and the tile plan needs their lengths), folds the raw byte
+// counts through the mode's symbol table to rank the codes as prepare() does,
+// and plans the panels on the raw lengths: an upper bound on the normalised
+// ones, the surplus blocks hold code 0.  It reads the option bytes once, to
+// count them, and copies them once.
+int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
+                 int mode, Arena &ar, Layout &L) {
+  uint8_t sym[256];
+  symbol_table(mode, sym);
+  std::vector<uint8_t> nq;
+  std::vector<int64_t> nOffB(nB + 1, 0);
+  nq.reserve((size_t)std::max<int64_t>(offB[nB], 0));
+  for (int j = 0; j < nB; j++) {
+    for (int64_t i = offB[j]; i < offB[j + 1]; i++)
+      if (sym[qs[i]]) nq.push_back(sym[qs[i]]);
+    nOffB[j + 1] = (int64_t)nq.size();
+  }
+  if (!query_lengths_ok(nOffB.data(), nB)) return -2;
+  const int nt = host_threads();
+  int64_t rawFreq[256], freq[256] = {0};
+  count_bytes(opts, offA[nA], nt, rawFreq);
+  for (int b = 0; b < 256; b++)
+    if (sym[b]) freq[sym[b]] += rawFreq[b];
+  uint8_t code[256];
+  int nsym = 0;
+  if (!rank_codes(freq, nq.data(), (int64_t)nq.size(), code, &nsym) || nsym > 63) return -8;  // 36 symbols: never
+  L.nA = nA;
+  L.nB = nB;
+  L.scaled = 1;
+
+  const PanelPlan panels = plan_panels(offA, nA);
+  L.nPanels = (int)panels.blocks.size();
+  const TilePlan tiles = plan_tiles(nOffB.data(), nB, L.kindStart, L.kindCount);
+  L.nTiles = (int)(tiles.q.size() / kTileSlots);
+  lay_out(L, panels.off[L.nPanels], offA[nA]);
+  if (int rc = ar.ensure(L.bytes)) return rc;
+
+  char *h = ar.host;
+  memcpy(h + L.oPanelOff, panels.off.data(), sizeof(int64_t) * panels.off.size());
+  memcpy(h + L.oPanelBlocks, panels.blocks.data(), sizeof(int) * panels.blocks.size());
+  int *perm = reinterpret_cast<int *>(h + L.oPerm);
+  memcpy(perm, panels.order.data(), sizeof(int) * (size_t)nA);
+  std::fill(perm + nA, perm + (size_t)L.nPanels * SLOTS, -1);
+  memcpy(h + L.oTileQ, tiles.q.data(), sizeof(int) * tiles.q.size());
+  memcpy(h + L.oTileLen, tiles.len.data(), sizeof(int) * tiles.len.size());
+  fill_tables(nq.data(), nOffB.data(), code, tiles, L, nt, h);
+  memcpy(h + L.oOffA, offA, sizeof(int64_t) * (size_t)(nA + 1));
+  uint8_t *byteMap = reinterpret_cast<uint8_t *>(h + L.oByteMap);
+  for (int b = 0; b < 256; b++) byteMap[b] = sym[b] ? (uint8_t)(code[sym[b]] * 4) : 0;
+  memcpy(h + L.oRaw, opts, (size_t)offA[nA]);
+  return 0;
+}
+
 int grid_x(int nPanels, int tiles) {
   // ~4k workgroups per launch: ~2 rounds of the 256 CUs x 7 resident 256-thread
   // groups, each walking enough panels to amortise staging its 4 KiB tile table
@@ -792,34 +988,56 @@ int launch_all(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
   return rc;
 }
 
-void record_times(Arena &ar, double prep) {
-  float a = 0, b = 0, c = 0;
+// The fill kernel of the normalising modes: one lane per panel slot.
+int launch_fill(const Layout &L, const Arena &ar, hipStream_t s) {
+  hipLaunchKernelGGL(ed_fill_panels_kernel, dim3(L.nPanels * (SLOTS / THREADS)), dim3(THREADS), 0, s,
+                     dev_at<const uint4>(ar, L.oRaw), dev_at<const int64_t>(ar, L.oOffA),
+                     dev_at<const int>(ar, L.oPerm), dev_at<const int64_t>(ar, L.oPanelOff),
+                     dev_at<const int>(ar, L.oPanelBlocks), dev_at<const uint32_t>(ar, L.oByteMap),
+                     dev_at<uint4>(ar, L.oPanels), dev_at<int>(ar, L.oLenSorted));
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// ev[0] .. ev[3] bracket H2D, the kernels and D2H; with a device fill ev[4]
+// lies between the fill kernel and the matcher kernels.
+void record_times(Arena &ar, double prep, bool deviceFill) {
+  float a = 0, b = 0, c = 0, f = 0;
   (void)hipEventElapsedTime(&a, ar.ev[0], ar.ev[1]);
-  (void)hipEventElapsedTime(&b, ar.ev[1], ar.ev[2]);
+  if (deviceFill) (void)hipEventElapsedTime(&f, ar.ev[1], ar.ev[4]);
+  (void)hipEventElapsedTime(&b, ar.ev[deviceFill ? 4 : 1], ar.ev[2]);
   (void)hipEventElapsedTime(&c, ar.ev[2], ar.ev[3]);
   ar.last[0] = prep;
   ar.last[1] = a;
   ar.last[2] = b;
   ar.last[3] = c;
+  ar.last[4] = f;
   if (getenv("M2K_ED_PROFILE"))
-    fprintf(stderr, "[m2k_ed] prep %.3f ms  h2d %.3f ms  kernel %.3f ms  d2h %.3f ms\n", prep, a, b, c);
+    fprintf(stderr, "[m2k_ed] prep %.3f ms  h2d %.3f ms  fill %.3f ms  kernel %.3f ms  d2h %.3f ms\n", prep, a, f, b,
+            c);
 }
 
 // One request: the distance matrix into outT when it is set, the closest
 // option per query into bestIdx / bestDist otherwise.
+// `mode` is MODE_NONE (the strings are matched as they are, the host fills the
+// panels) or a normalising mode (raw strings in, the device fills the panels
+// under the mode's byte map; the query limit then applies to the normalised
+// query).
 //   step                                 returns
+//   unknown mode                         -9
 //   no device                            -1
 //   nothing to compute                   0 (closest without options: -1 / -1 per query)
 //   prepare                              -2 query too long, -8 no free byte code, -4 arena
 //   matrix: device output buffer         -4
 //   H2D copy                             -7, at once (no sync)
 //   closest: memset of `best`            -4, at once (no sync)
-//   a kernel launch                      -5  } later launches and the D2H copy are
+//   a kernel launch (the fill included)  -5  } later launches and the D2H copy are
 //   D2H copy                             -7  } skipped, the stream is synchronised
 //   stream synchronise                   -6 (when nothing failed before)
 // Timings are recorded on success only.
 int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-        int32_t *outT, int32_t *bestIdx, int32_t *bestDist) {
+        int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE) {
+  if (mode != MODE_NONE && mode != MODE_ALNUM_LOWER) return -9;
+  const bool deviceFill = mode != MODE_NONE;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
   if (nB <= 0 || (outT && nA <= 0)) return 0;
@@ -831,7 +1049,8 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
   std::lock_guard<std::mutex> lock(ar.mu);
   const double t0 = now_ms();
   Layout L;
-  int rc = prepare(opts, offA, nA, qs, offB, nB, ar, L);
+  int rc = deviceFill ? prepare_norm(opts, offA, nA, qs, offB, nB, mode, ar, L)
+                      : prepare(opts, offA, nA, qs, offB, nB, ar, L);
   if (rc) return rc;
   if (outT && (rc = ar.ensure_out(sizeof(int) * (size_t)nA * nB))) return rc;
   const double prep = now_ms() - t0;
@@ -842,7 +1061,11 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
   if (!outT && hipMemsetAsync(best, 0xff, sizeof(u64) * nB, s) != hipSuccess) return -4;
   (void)hipEventRecord(ar.ev[1], s);
   int *out = outT ? ar.out : nullptr;
-  rc = L.scaled ? launch_all<true>(L, ar, out, s) : launch_all<false>(L, ar, out, s);
+  if (deviceFill) {
+    rc = launch_fill(L, ar, s);
+    (void)hipEventRecord(ar.ev[4], s);
+  }
+  if (rc == 0) rc = L.scaled ? launch_all<true>(L, ar, out, s) : launch_all<false>(L, ar, out, s);
   (void)hipEventRecord(ar.ev[2], s);
   if (rc == 0) {
     const hipError_t e = outT ? hipMemcpyAsync(outT, out, sizeof(int) * (size_t)nA * nB, hipMemcpyDeviceToHost, s)
@@ -857,7 +1080,7 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
       bestIdx[j] = (int32_t)(hBest[j] & 0xffffffffULL);
       bestDist[j] = (int32_t)(hBest[j] >> 32);
     }
-  record_times(ar, prep);
+  record_times(ar, prep, deviceFill);
   return 0;
 }
 
@@ -880,11 +1103,33 @@ int m2k_ed_closest(const uint8_t *opts, const int64_t *offA, int nA, const uint8
   return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist);
 }
 
+// The same two on raw strings under a normalising mode (1 = ALNUM_LOWER: keep
+// 0-9 a-z A-Z, fold A-Z to a-z, drop every other byte): the distances are those
+// of the normalised strings.  The queries must be <= 256 bytes after
+// normalisation (-2 otherwise); an unknown mode returns -9.
+int m2k_ed_matrix_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB,
+                       int nB, int mode, int32_t *outT) {
+  return run(opts, offA, nA, qs, offB, nB, outT, nullptr, nullptr, mode);
+}
+
+int m2k_ed_closest_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB,
+                        int nB, int mode, int32_t *bestIdx, int32_t *bestDist) {
+  return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode);
+}
+
 // prep / H2D / kernel / D2H milliseconds of the last successful call
 void m2k_ed_last_timings(double *out4) {
   Arena &ar = arena();
   std::lock_guard<std::mutex> lock(ar.mu);
   for (int i = 0; i < 4; i++) out4[i] = ar.last[i];
+}
+
+// Milliseconds of the fill kernel in the last successful call (0 when the host
+// filled the panels); the kernel time above does not include it.
+double m2k_ed_last_fill_ms() {
+  Arena &ar = arena();
+  std::lock_guard<std::mutex> lock(ar.mu);
+  return ar.last[4];
 }
 
 int m2k_gpu_device_count() {

@@ -10,6 +10,7 @@ import os
 import sys
 
 from . import native
+from ..utils.lazyre import lazy as _lazy_re
 
 # numpy and the HIP wrapper (which needs numpy) are imported on first use:
 # importing numpy costs more than the handful of matches a CLI run makes
@@ -71,12 +72,39 @@ def wagner_fischer_py(a, b, icost=1, dcost=1, scost=2):
     return row1[len(b)]
 
 
-def _use_gpu(pairs, device, queries):
+# ``normalize="alnum_lower"``: the distances are those of the strings with every
+# character outside [a-zA-Z0-9] removed and the rest lower-cased, which is what
+# the reference's GetClosestMatchingString compares (utils.go:377-401).  What
+# is left is ASCII, so ``str.lower`` is Go's ``strings.ToLower`` here.  The GPU
+# path takes the raw strings and normalises on the device.
+_NON_ALNUM_RE = _lazy_re(r"[^a-zA-Z0-9]+")
+
+
+def _check_normalize(normalize):
+    if normalize not in (None, "alnum_lower"):
+        raise ValueError("normalize must be None or 'alnum_lower', not %r" % (normalize,))
+
+
+def normalize_alnum_lower(s):
+    if not isinstance(s, str):
+        s = bytes(s).decode("utf-8", "surrogateescape")
+    return _NON_ALNUM_RE.sub("", s).lower()
+
+
+def _normalized(strings, normalize):
+    return [normalize_alnum_lower(s) for s in strings] if normalize else strings
+
+
+def _use_gpu(pairs, device, queries, normalize=None):
     if device == "cpu":
         return False
     if device != "gpu" and pairs < GPU_MIN_PAIRS:
         return False
     gpu = _gpu()
+    if normalize:   # the limit applies after normalisation: the kernel library checks it
+        if device == "gpu":
+            return True
+        return gpu.gpu_host() and (pairs >= GPU_MIN_PAIRS_COLD or _gpu_warm())
     # the limit belongs to the kernel library; one that states none has the single-word kernels' 64
     limit = getattr(gpu, "MAX_QUERY_BYTES", 64)
     fits = all(len(q.encode("utf-8", "surrogateescape") if isinstance(q, str) else q) <= limit for q in queries)
@@ -94,18 +122,20 @@ def _threads():
     return host_threads(16)
 
 
-def matrix(options, queries, device="auto"):
+def matrix(options, queries, device="auto", normalize=None):
     """Distance matrix, int32 array of shape [len(options), len(queries)].
 
-    device: "auto" | "cpu" | "gpu"."""
+    device: "auto" | "cpu" | "gpu"; normalize: None | "alnum_lower"."""
+    _check_normalize(normalize)
     na, nb = len(options), len(queries)
-    if _use_gpu(na * nb, device, queries):
+    if _use_gpu(na * nb, device, queries, normalize):
         gpu = _gpu()
         try:
-            return gpu.ed_matrix(options, queries)
+            return gpu.ed_matrix_normalized(options, queries) if normalize else gpu.ed_matrix(options, queries)
         except gpu.GpuUnsupportedInput:
             if device == "gpu":
                 raise
+    options, queries = _normalized(options, normalize), _normalized(queries, normalize)
     m = native.module()
     if m is not None:
         return m.edit_distance_batch(list(options), list(queries), 1, 1, 2, _threads())
@@ -113,21 +143,23 @@ def matrix(options, queries, device="auto"):
     return np.array([[wagner_fischer_py(o, q) for q in queries] for o in options], dtype=np.int32).reshape(na, nb)
 
 
-def closest_indices(options, queries, device="auto"):
+def closest_indices(options, queries, device="auto", normalize=None):
     """For every query the index of the first option with the minimum distance
     and that distance (int32 arrays; -1 when there are no options).  The argmin
     is fused into the distance computation (GPU kernel or native CPU)."""
+    _check_normalize(normalize)
     na, nb = len(options), len(queries)
     np = _np()
     if na == 0 or nb == 0:
         return np.full(nb, -1, dtype=np.int32), np.full(nb, -1, dtype=np.int32)
-    if _use_gpu(na * nb, device, queries):
+    if _use_gpu(na * nb, device, queries, normalize):
         gpu = _gpu()
         try:
-            return gpu.ed_closest(options, queries)
+            return gpu.ed_closest_normalized(options, queries) if normalize else gpu.ed_closest(options, queries)
         except gpu.GpuUnsupportedInput:
             if device == "gpu":
                 raise
+    options, queries = _normalized(options, normalize), _normalized(queries, normalize)
     m = native.module()
     if m is not None:
         return m.closest_batch(list(options), list(queries), _threads())
@@ -148,15 +180,17 @@ def _closest_py(options, queries):
     return idx, dist
 
 
-def closest_index_list(options, queries, device="auto"):
+def closest_index_list(options, queries, device="auto", normalize=None):
     """:func:`closest_indices` as two Python lists.  Below the GPU threshold
     this path never imports numpy (the native ``closest_list``)."""
+    _check_normalize(normalize)
     na, nb = len(options), len(queries)
     if na == 0 or nb == 0:
         return [-1] * nb, [-1] * nb
-    if _use_gpu(na * nb, device, queries):
-        idx, dist = closest_indices(options, queries, device)
+    if _use_gpu(na * nb, device, queries, normalize):
+        idx, dist = closest_indices(options, queries, device, normalize)
         return [int(i) for i in idx], [int(d) for d in dist]
+    options, queries = _normalized(options, normalize), _normalized(queries, normalize)
     m = native.module()
     if m is not None:
         return m.closest_list(list(options), list(queries), _threads())

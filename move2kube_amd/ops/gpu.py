@@ -80,6 +80,14 @@ def _open_library():
     lib.m2k_ed_matrix.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int, i32p]
     lib.m2k_ed_closest.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int, i32p,
                                    i32p]
+    if hasattr(lib, "m2k_ed_closest_norm"):   # absent from an earlier build named by the benchmark's --lib
+        lib.m2k_ed_matrix_norm.restype = lib.m2k_ed_closest_norm.restype = ctypes.c_int
+        lib.m2k_ed_matrix_norm.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int,
+                                           ctypes.c_int, i32p]
+        lib.m2k_ed_closest_norm.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int,
+                                            ctypes.c_int, i32p, i32p]
+        lib.m2k_ed_last_fill_ms.restype = ctypes.c_double
+        lib.m2k_ed_last_fill_ms.argtypes = []
     lib.m2k_ed_last_timings.restype = None
     lib.m2k_ed_last_timings.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.m2k_gpu_device_count.restype = ctypes.c_int
@@ -105,11 +113,15 @@ def warm():
 
 
 def last_timings():
-    """{prep, h2d, kernel, d2h} milliseconds of the last ed_matrix/ed_closest call."""
+    """{prep, h2d, kernel, d2h, fill} milliseconds of the last kernel call.
+    ``kernel_ms`` is the matcher kernels; ``fill_ms`` is the device panel fill
+    of the ``*_normalized`` calls (0 for the others, whose fill is in ``prep_ms``)."""
     lib = _lib_or_raise()
     buf = (ctypes.c_double * 4)()
     lib.m2k_ed_last_timings(buf)
-    return dict(zip(("prep_ms", "h2d_ms", "kernel_ms", "d2h_ms"), (round(x, 3) for x in buf)))
+    out = dict(zip(("prep_ms", "h2d_ms", "kernel_ms", "d2h_ms"), (round(x, 3) for x in buf)))
+    out["fill_ms"] = round(lib.m2k_ed_last_fill_ms(), 3) if hasattr(lib, "m2k_ed_last_fill_ms") else 0.0
+    return out
 
 
 def device_arch():
@@ -187,3 +199,52 @@ def ed_closest(options, queries):
     global _warm
     _warm = True
     return idx, dist
+
+
+# Normalising modes of the kernel library (``run()`` in ``ed_kernel.hip``).
+ALNUM_LOWER = 1
+
+
+def ed_matrix_normalized(options, queries, mode=ALNUM_LOWER):
+    """:func:`ed_matrix` of the normalised strings, from the raw ones: keep
+    ``0-9 a-z A-Z``, fold to lower case, drop every other byte.  The options are
+    normalised on the device as their panels are filled; MAX_QUERY_BYTES applies
+    to the normalised queries."""
+    lib = _lib_or_raise()
+    na, nb = len(options), len(queries)
+    if na == 0 or nb == 0:
+        return np.zeros((na, nb), dtype=np.int32)
+    a, offa, _ = _pack(options)
+    q, offb, _ = _pack(queries)
+    outT = np.empty((nb, na), dtype=np.int32)
+    rc = lib.m2k_ed_matrix_norm(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode,
+                                _ptr(outT, ctypes.c_int32))
+    _check_norm_rc("m2k_ed_matrix_norm", rc)
+    return outT.T
+
+
+def ed_closest_normalized(options, queries, mode=ALNUM_LOWER):
+    """:func:`ed_closest` of the normalised strings, from the raw ones (see
+    :func:`ed_matrix_normalized`)."""
+    lib = _lib_or_raise()
+    na, nb = len(options), len(queries)
+    idx = np.full(nb, -1, dtype=np.int32)
+    dist = np.full(nb, -1, dtype=np.int32)
+    if nb == 0 or na == 0:
+        return idx, dist
+    a, offa, _ = _pack(options)
+    q, offb, _ = _pack(queries)
+    rc = lib.m2k_ed_closest_norm(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode,
+                                 _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    _check_norm_rc("m2k_ed_closest_norm", rc)
+    return idx, dist
+
+
+def _check_norm_rc(name, rc):
+    global _warm
+    if rc in _RC_UNSUPPORTED:
+        raise GpuUnsupportedInput("%s cannot take this input (code %d; queries normalise to <= %d bytes)"
+                                  % (name, rc, MAX_QUERY_BYTES))
+    if rc != 0:
+        raise GpuUnavailable("%s failed with code %d" % (name, rc))
+    _warm = True

@@ -449,9 +449,6 @@ def write_template_to_file(tpl, config, write_path, mode):
     write_text(write_path, get_string_from_template(tpl, config), mode)
 
 
-_TOKEN_RE = _lazy_re(r"[^a-zA-Z0-9]+")
-
-
 def get_closest_matching_string(options, search):
     """Option with least Wagner-Fischer distance (ins=1, del=1, sub=2) to ``search``
     after stripping non-alphanumerics and lower-casing (``utils.go:377-401``)."""
@@ -877,11 +874,11 @@ def go_bool_str(b):
 
 def get_closest_matching_strings(options, searches):
     """Batched :func:`get_closest_matching_string`: one fused distance+argmin pass
-    (gfx950 kernel when large, native bit-parallel CPU otherwise)."""
+    (gfx950 kernel when large, native bit-parallel CPU otherwise).  The names go
+    down as they are: the matcher strips and lower-cases (on the device when the
+    batch runs there)."""
     from ..ops import editdistance
     if not options or not searches:
         return [""] * len(searches)
-    toks = [go_lower(_TOKEN_RE.sub("", o)) for o in options]
-    qs = [go_lower(_TOKEN_RE.sub("", s)) for s in searches]
-    idx, _ = editdistance.closest_index_list(toks, qs)
+    idx, _ = editdistance.closest_index_list(list(options), list(searches), normalize="alnum_lower")
     return [options[i] for i in idx]
