@@ -96,7 +96,14 @@ def main():
     ap.add_argument("--raw", action="store_true",
                     help="names with separators and mixed case: Python normalisation + ed_closest against "
                          "ed_closest_normalized (medians over --reps, the routes checked against each other)")
+    ap.add_argument("--costs", default="1,1,2",
+                    help="insert,delete,substitute: 1,1,2 (the LCS kernels) or 1,1,1 (the Levenshtein kernels); "
+                         "--cpu then times the native scalar DP and takes the first minimum per query")
     a = ap.parse_args()
+    costs = tuple(int(c) for c in a.costs.split(","))
+    if costs not in ((1, 1, 2), (1, 1, 1)):
+        raise SystemExit("--costs is 1,1,2 or 1,1,1")
+    kw = {"metric": gpu.LEVENSHTEIN} if costs == (1, 1, 1) else {}
     if a.lib:
         gpu.LIB_PATH = os.path.abspath(a.lib)
     if a.raw:
@@ -110,7 +117,8 @@ def main():
     opts = words(rng, a.options, 4, 40)
     qs = words(rng, a.queries, min(a.qmin, a.qmax), a.qmax)
     res = {"options": a.options, "queries": a.queries, "qmin": min(a.qmin, a.qmax), "qmax": a.qmax,
-           "pairs": a.options * a.queries, "option_bytes": sum(len(o) for o in opts), "lib": os.path.basename(a.lib) if a.lib else "in-tree"}
+           "pairs": a.options * a.queries, "option_bytes": sum(len(o) for o in opts), "lib": os.path.basename(a.lib) if a.lib else "in-tree",
+           "costs": list(costs)}
     cells = sum(len(o) for o in opts) * a.queries  # option bytes x queries = bit-parallel steps
     if gpu.available():
         gpu.ed_closest(opts[:1024], qs[:8])  # warm-up / context creation
@@ -118,7 +126,7 @@ def main():
             t, k = [], []
             for _ in range(a.reps):
                 t0 = time.perf_counter()
-                r = fn(opts, qs)
+                r = fn(opts, qs, **kw)
                 t.append(time.perf_counter() - t0)
                 k.append(gpu.last_timings()["kernel_ms"])
             res["gpu_%s_s" % name] = min(t)
@@ -126,11 +134,16 @@ def main():
             res["gpu_%s_breakdown" % name] = gpu.last_timings()
             res["gpu_%s_gsteps_per_s" % name] = cells / min(t) / 1e9
         res["arch"] = gpu.device_arch()
-        gi, gd = gpu.ed_closest(opts, qs)
+        gi, gd = gpu.ed_closest(opts, qs, **kw)
     if a.cpu and native.available():
         th = min(16, os.cpu_count() or 1)
         t0 = time.perf_counter()
-        ci, cd = native.module().closest_batch(opts, qs, th)
+        if kw:   # no fused argmin for these costs on the CPU: the matrix, then its first minimum per query
+            d = native.module().edit_distance_batch(opts, qs, costs[0], costs[1], costs[2], th)
+            ci = d.argmin(axis=0)
+            cd = d.min(axis=0)
+        else:
+            ci, cd = native.module().closest_batch(opts, qs, th)
         res["cpu_native_closest_s"] = time.perf_counter() - t0
         res["cpu_threads"] = th
         if gpu.available():

@@ -1,5 +1,6 @@
-// Batched weighted edit distance (Wagner-Fischer with ins=1, del=1, sub=2) and
-// fused closest-match search on MI355X (gfx950).
+// Batched weighted edit distance (Wagner-Fischer with ins=1, del=1, sub=2, and
+// as a second metric unit-cost Levenshtein distance) and fused closest-match
+// search on MI355X (gfx950).
 //
 // Used by the fuzzy matcher behind common.GetClosestMatchingString
 // (reference internal/common/utils.go:377-401), which the CF container-types
@@ -64,6 +65,63 @@
 //    transposed view); it is bound by the scattered int32 stores and, end to
 //    end, by the device-to-host copy of the matrix itself.
 //  * Tiles are launched in slabs of <= 65535 (gridDim.y limit).
+//
+// Second metric: unit-cost Levenshtein distance (ins = del = sub = 1), the
+// METRIC template parameter of both kernels and of for_each_option.  It is
+// Myers' bit-vector recurrence in Hyyro's form with the DP column over the
+// query: two vectors per column word, Pv (vertical +1) and Mv (vertical -1),
+// from Pv = ~0, Mv = 0, and after the option's last character
+//   dist = |a| + popc(Pv & mask(len)) - popc(Mv & mask(len)).
+// Code map, panels (host or device fill), mask tables in LDS, the ds_read_b64
+// scheme, the XCD remap, the argmin and the slab launches are the LCS
+// kernels'; the host side does not know the metric until it launches.  What
+// is this family's own:
+//  * Padding is not neutral.  A character that matches nothing still adds a DP
+//    column, so a lane steps exactly lenSorted[slot] characters (read before
+//    the panel walk).  Chosen shape, at 4-character granularity because a
+//    lane's 16-byte block arrives as four words: a word that both of the
+//    lane's options still fill goes through the unrolled path with the two
+//    chains interleaved; the one word in which an option ends runs a counted
+//    loop of <= 3 steps under the exec mask; words behind the end do nothing,
+//    and a lane stops loading blocks after its longer option's last one.
+//    Per-character predication of the state was not built: it costs two
+//    v_cndmask_b32 per column word and character (a fifth on top of the ten
+//    below) on every character, and steps through all padding besides.
+//  * Word steps (myers_step16 / myers_step).  K16 keeps two queries per word
+//    with v_pk_add_u16 and v_pk_lshlrev_b16 and ors 0x00010001 into Ph.  Every
+//    other class is a run of 32-bit words per query (1, 2, 4, 8): the add is
+//    v_add_co_u32 + v_addc_co_u32 (__builtin_addc, as in lcs_step_wide), both
+//    shifts take the bit from the word below with one v_alignbit_b32, and the
+//    three-input forms are v_bitop3_b32.
+//  * Registers.  Four state vectors per lane (Pv, Mv x two options) instead of
+//    two.  Every class keeps two options per lane and compiles without
+//    scratch, K256 included (96 VGPRs), so no class was cut to one option.
+//    As compiled (hipcc -O3, gfx950, -save-temps), matrix / closest kernels,
+//    the same for SCALED and not:
+//             VGPR      SGPR      LDS bytes     scratch
+//      K16    64 / 80   74 / 50   4096 / 4352   0
+//      K32    64 / 72   54 / 42   4096 / 4224   0
+//      K64    64 / 68   46 / 42   4096 / 4160   0
+//      K128   93 / 97   50 / 46   8192 / 8256   0
+//      K256   94 / 96   46 / 47   8192 / 8224   0
+//    (Fewer resident waves than the LCS kernels' 8 per SIMD wherever a
+//    kernel takes more than 64 VGPRs.)  The 20 LCS kernels keep their
+//    figures: VGPR 39/39/41/53/57 matrix and 54/46/43/56/58 closest, no
+//    scratch.
+//  * Instruction mix, closest kernels, over the kernel's 40 character bodies
+//    (32 unrolled + 8 in the counted loops).  K32 (4 column words): 80
+//    ds_read_b64, 640 v_bitop3_b32, 355 v_and_b32, 363 v_or_b32, 344
+//    v_lshlrev_b32, 179 v_add_u32: 11.6 VALU per word and character (the
+//    compiler folds Mv' = Ph & (Eq | Mv) into a fourth bitop3 and splits
+//    (Ph << 1) | 1 into shift + or).  K256 (8 words, one query): 160
+//    ds_read_b64, 1280 v_bitop3_b32, 690 v_and_b32, 482 v_or_b32, 560
+//    v_alignbit_b32, 43 v_add_co_u32 + 282 v_addc_co_u32, 103 v_lshlrev_b32:
+//    10.8 per word and character; no compare-and-select carries.
+//  * Measured (200k options x 2048 queries, MI355X, closest kernels, ps per
+//    option byte x query x u64 column word): K16 0.67, K32 0.62, K64 0.58,
+//    K128 0.56, K256 0.53 against the LCS kernels' 0.32 / 0.23 / 0.24 / 0.22 /
+//    0.21 in the same runs: 2.1 to 2.7 times the LCS time per character.  See
+//    docs/history.md.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -299,6 +357,193 @@ __device__ __forceinline__ int query_lcs(const typename TileT<KIND>::W (&V)[Tile
   }
 }
 
+// ---------------------------------------------------------------------------
+// The second metric: unit-cost Levenshtein distance (ins = del = sub = 1) by
+// Myers' bit-vector recurrence in Hyyro's form.  Tables, panels and tiles are
+// the LCS kernels'; what differs is the column (two vectors: Pv = vertical +1,
+// Mv = vertical -1), the step, and that a lane counts its characters.
+// ---------------------------------------------------------------------------
+enum { METRIC_INDEL2 = 0, METRIC_LEVENSHTEIN = 1 };
+
+// v_bitop3_b32 truth tables, written over the operands' own tables.
+enum { BIT_A = 0xF0, BIT_B = 0xCC, BIT_C = 0xAA };
+constexpr int kXorOr = ((BIT_A ^ BIT_B) | BIT_C) & 0xFF;   // (a ^ b) | c
+constexpr int kOrNor = (BIT_A | ~(BIT_B | BIT_C)) & 0xFF;  // a | ~(b | c)
+
+// The column of one option against a tile, in 32-bit words: NH = 2 per
+// sub-table, HPQ of them to a query (K16: two queries to a word instead).
+template <int KIND>
+struct LevColumn {
+  enum { NH = 2 * TileT<KIND>::NSUB, HPQ = KIND == K16 ? 1 : TileT<KIND>::MAXLEN / 32 };
+  uint32_t Pv[NH], Mv[NH];
+};
+
+// One character against the two 16-bit columns of a K16 word: the add and both
+// shifts are packed 16-bit operations, so nothing crosses from the low query
+// into the high one, and each half of Ph gets its own 1.
+__device__ __forceinline__ void myers_step16(uint32_t &Pv, uint32_t &Mv, uint32_t eq) {
+  const uint32_t sum = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, eq & Pv) + __builtin_bit_cast(u16x2, Pv));
+  const uint32_t xh = __builtin_amdgcn_bitop3_b32(sum, Pv, eq, kXorOr);
+  const uint32_t ph = __builtin_amdgcn_bitop3_b32(Mv, xh, Pv, kOrNor);
+  const uint32_t mh = Pv & xh;
+  const uint32_t phs = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, ph) << 1) | 0x00010001u;
+  const uint32_t mhs = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, mh) << 1);
+  const uint32_t xv = eq | Mv;
+  Pv = __builtin_amdgcn_bitop3_b32(mhs, xv, phs, kOrNor);
+  Mv = phs & xv;
+}
+
+// One character against a query's column of N 32-bit words (N = 1 for K32 up
+// to 8 for K256).  Two things link the words, both upward only: the addition
+// (v_add_co_u32 + v_addc_co_u32, the carry out of the top word is dropped) and
+// the two shifts, which take bit 31 of the word below through v_alignbit_b32;
+// the lowest word of Ph shifts a 1 in (v_lshl_or_b32).  Ten VALU operations
+// per word whatever N is.  Bits above the query's length hold garbage that
+// never comes down; query_lev masks it off.
+template <int N>
+__device__ __forceinline__ void myers_step(uint32_t *Pv, uint32_t *Mv, const uint32_t *eq) {
+  uint32_t xh[N];
+  unsigned carry = 0;
+#pragma unroll
+  for (int h = 0; h < N; h++) {
+    const uint32_t sum = __builtin_addc(eq[h] & Pv[h], Pv[h], carry, &carry);
+    xh[h] = __builtin_amdgcn_bitop3_b32(sum, Pv[h], eq[h], kXorOr);
+  }
+  uint32_t phBelow = 0, mhBelow = 0;
+#pragma unroll
+  for (int h = 0; h < N; h++) {
+    const uint32_t ph = __builtin_amdgcn_bitop3_b32(Mv[h], xh[h], Pv[h], kOrNor);
+    const uint32_t mh = Pv[h] & xh[h];
+    const uint32_t phs = h == 0 ? (ph << 1) | 1u : __builtin_amdgcn_alignbit(ph, phBelow, 31);
+    const uint32_t mhs = h == 0 ? mh << 1 : __builtin_amdgcn_alignbit(mh, mhBelow, 31);
+    phBelow = ph;
+    mhBelow = mh;
+    const uint32_t xv = eq[h] | Mv[h];
+    Pv[h] = __builtin_amdgcn_bitop3_b32(mhs, xv, phs, kOrNor);
+    Mv[h] = phs & xv;
+  }
+}
+
+// One coded character against every query of the tile: the LDS reads of step4
+// (same offsets, same conflict-free ds_read_b64), then the Myers steps.
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void lev_char(uint32_t c, const char *T, LevColumn<KIND> &C) {
+  typedef TileT<KIND> TT;
+  typedef LevColumn<KIND> Col;
+  const uint32_t off = SCALED ? c * 2u : c * 8u;
+  uint32_t offh[TT::NSUB], eq[Col::NH];
+  offh[0] = off;
+#pragma unroll
+  for (int h = 1; h < TT::NSUB; h++) {
+    offh[h] = off + kSubTableBytes * h;
+    __asm__ volatile("" : "+v"(offh[h]));
+  }
+#pragma unroll
+  for (int h = 0; h < TT::NSUB; h++) {
+    const u64 m = *reinterpret_cast<const u64 *>(T + offh[h]);
+    eq[2 * h] = (uint32_t)m;
+    eq[2 * h + 1] = (uint32_t)(m >> 32);
+  }
+  if constexpr (KIND == K16) {
+#pragma unroll
+    for (int k = 0; k < Col::NH; k++) myers_step16(C.Pv[k], C.Mv[k], eq[k]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < Col::NH; q += Col::HPQ) myers_step<Col::HPQ>(&C.Pv[q], &C.Mv[q], &eq[q]);
+  }
+}
+
+// Four characters of both of the lane's options (word `w0` of option 0's
+// block, `w1` of option 1's), of which the options still have r0 and r1 left
+// (<= 0: the option ended).  A padding character is not neutral here - it
+// would add a DP column - so a lane steps exactly its option's length: whole
+// words go through the unrolled path, the two chains interleaved as in
+// panel_lcs; the one word in which an option ends runs a counted loop of at
+// most three steps under the exec mask, and words behind the end do nothing.
+// Options of a panel are sorted by length, so a wave's lanes nearly always
+// take the same side.
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void lev_word(uint32_t w0, uint32_t w1, int r0, int r1, const char *T,
+                                         LevColumn<KIND> (&C)[OPT_PER_THREAD]) {
+  if (r0 >= 4 && r1 >= 4) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      lev_char<KIND, SCALED>((w0 >> (8 * i)) & 0xffu, T, C[0]);
+      lev_char<KIND, SCALED>((w1 >> (8 * i)) & 0xffu, T, C[1]);
+    }
+  } else {
+    const uint32_t w[OPT_PER_THREAD] = {w0, w1};
+    const int r[OPT_PER_THREAD] = {r0, r1};
+#pragma unroll
+    for (int u = 0; u < OPT_PER_THREAD; u++) {
+      uint32_t rest = w[u];
+      const int n = r[u] < 4 ? r[u] : 4;
+#pragma clang loop unroll(disable)
+      for (int i = 0; i < n; i++) {
+        lev_char<KIND, SCALED>(rest & 0xffu, T, C[u]);
+        rest >>= 8;
+      }
+    }
+  }
+}
+
+// Myers columns of this lane's OPT_PER_THREAD options (lengths la[u], in hand
+// before the walk) in one panel against the tile.  The lane walks the blocks
+// its longer option needs, never more than the panel has.
+template <int KIND, bool SCALED>
+__device__ __forceinline__ void panel_lev(const uint4 *__restrict__ panel, int blocks, const char *T,
+                                          const int (&la)[OPT_PER_THREAD], LevColumn<KIND> (&C)[OPT_PER_THREAD]) {
+  static_assert(OPT_PER_THREAD == 2, "lev_word takes the lane's two options");
+  const int lane = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < OPT_PER_THREAD; u++)
+#pragma unroll
+    for (int k = 0; k < LevColumn<KIND>::NH; k++) {
+      C[u].Pv[k] = ~0u;
+      C[u].Mv[k] = 0u;
+    }
+  const int mine = ((la[0] > la[1] ? la[0] : la[1]) + 15) >> 4;
+  const int n = mine < blocks ? mine : blocks;
+  if (n == 0) return;
+  uint4 cur[OPT_PER_THREAD], nxt[OPT_PER_THREAD];
+#pragma unroll
+  for (int u = 0; u < OPT_PER_THREAD; u++) cur[u] = panel[u * THREADS + lane];
+  for (int b = 0; b < n; b++) {
+    if (b + 1 < n) {
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) nxt[u] = panel[(size_t)(b + 1) * SLOTS + u * THREADS + lane];
+    }
+    const int r0 = la[0] - 16 * b, r1 = la[1] - 16 * b;
+    lev_word<KIND, SCALED>(cur[0].x, cur[1].x, r0, r1, T, C);
+    lev_word<KIND, SCALED>(cur[0].y, cur[1].y, r0 - 4, r1 - 4, T, C);
+    lev_word<KIND, SCALED>(cur[0].z, cur[1].z, r0 - 8, r1 - 8, T, C);
+    lev_word<KIND, SCALED>(cur[0].w, cur[1].w, r0 - 12, r1 - 12, T, C);
+#pragma unroll
+    for (int u = 0; u < OPT_PER_THREAD; u++) cur[u] = nxt[u];
+  }
+}
+
+// Distance of tile query j (length len) to an option of length la from the
+// final column: the bottom cell is la (the top row's value) plus the column's
+// vertical deltas over the query's own bits.
+template <int KIND>
+__device__ __forceinline__ int query_lev(const LevColumn<KIND> &C, int j, int len, int la) {
+  if constexpr (KIND == K16) {
+    const uint32_t mask = (1u << len) - 1u;  // len <= 16
+    const int sh = 16 * (j & 1);
+    return la + __popc((C.Pv[j >> 1] >> sh) & mask) - __popc((C.Mv[j >> 1] >> sh) & mask);
+  } else {
+    int d = la;
+#pragma unroll
+    for (int h = 0; h < LevColumn<KIND>::HPQ; h++) {
+      const int bits = len - 32 * h;
+      const uint32_t mask = bits >= 32 ? ~0u : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+      d += __popc(C.Pv[j * LevColumn<KIND>::HPQ + h] & mask) - __popc(C.Mv[j * LevColumn<KIND>::HPQ + h] & mask);
+    }
+    return d;
+  }
+}
+
 // Stage the tile's mask tables in LDS.  `tileM` is the table of the launch's
 // first tile and the launch's tiles are one class, so tile number `tile` of
 // the launch (blockIdx.y) lies `tile` tables further on.
@@ -314,7 +559,7 @@ __device__ __forceinline__ void load_tile(const uint4 *__restrict__ tileM, int t
 // option's original index and dist(j) = its distance to the tile's query j.
 // Tile metadata: tileQ[t][kTileSlots] = query index (-1 = empty), tileLen[t][kTileSlots]
 // = its length, t counted from the launch's first tile like the tables.
-template <int KIND, bool SCALED, class F>
+template <int KIND, bool SCALED, int METRIC, class F>
 __device__ __forceinline__ void for_each_option(
     const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
     const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
@@ -327,25 +572,40 @@ __device__ __forceinline__ void for_each_option(
 #pragma unroll
   for (int j = 0; j < TT::NQ; j++) qlen[j] = tileLen[tile * kTileSlots + j];
   for (int p = remap_panel(blockIdx.x, gridDim.x); p < nPanels; p += gridDim.x) {
-    typename TT::W V[OPT_PER_THREAD][TT::NW];
-    panel_lcs<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), V);
+    if constexpr (METRIC == METRIC_LEVENSHTEIN) {
+      int la[OPT_PER_THREAD];  // an empty slot has length 0: it steps nothing
 #pragma unroll
-    for (int u = 0; u < OPT_PER_THREAD; u++) {
-      const int s = p * SLOTS + u * THREADS + threadIdx.x;
-      const int o = perm[s];
-      if (o < 0) continue;
-      const int la = lenSorted[s];
-      auto dist = [&](int j) __attribute__((always_inline)) {
-        return la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
-      };
-      f(o, dist);
+      for (int u = 0; u < OPT_PER_THREAD; u++) la[u] = lenSorted[p * SLOTS + u * THREADS + threadIdx.x];
+      LevColumn<KIND> C[OPT_PER_THREAD];
+      panel_lev<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), la, C);
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) {
+        const int o = perm[p * SLOTS + u * THREADS + threadIdx.x];
+        if (o < 0) continue;
+        auto dist = [&](int j) __attribute__((always_inline)) { return query_lev<KIND>(C[u], j, qlen[j], la[u]); };
+        f(o, dist);
+      }
+    } else {
+      typename TT::W V[OPT_PER_THREAD][TT::NW];
+      panel_lcs<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), V);
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) {
+        const int s = p * SLOTS + u * THREADS + threadIdx.x;
+        const int o = perm[s];
+        if (o < 0) continue;
+        const int la = lenSorted[s];
+        auto dist = [&](int j) __attribute__((always_inline)) {
+          return la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
+        };
+        f(o, dist);
+      }
     }
   }
 }
 
 }  // namespace
 
-template <int KIND, bool SCALED>
+template <int KIND, bool SCALED, int METRIC>
 __global__ __launch_bounds__(THREADS) void ed_matrix_kernel(
     const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
     const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
@@ -360,10 +620,10 @@ __global__ __launch_bounds__(THREADS) void ed_matrix_kernel(
     for (int j = 0; j < TT::NQ; j++)
       if (qid[j] >= 0) outT[(size_t)qid[j] * nA + o] = dist(j);
   };
-  for_each_option<KIND, SCALED>(panels, panelOff, panelBlocks, lenSorted, perm, tileM, tileLen, nPanels, store);
+  for_each_option<KIND, SCALED, METRIC>(panels, panelOff, panelBlocks, lenSorted, perm, tileM, tileLen, nPanels, store);
 }
 
-template <int KIND, bool SCALED>
+template <int KIND, bool SCALED, int METRIC>
 __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
     const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
     const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
@@ -380,7 +640,7 @@ __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
       key[j] = k < key[j] ? k : key[j];
     }
   };
-  for_each_option<KIND, SCALED>(panels, panelOff, panelBlocks, lenSorted, perm, tileM, tileLen, nPanels, keep_min);
+  for_each_option<KIND, SCALED, METRIC>(panels, panelOff, panelBlocks, lenSorted, perm, tileM, tileLen, nPanels, keep_min);
   // argmin per query: wave shuffles, then the 4 waves through LDS, one atomic each
 #pragma unroll
   for (int j = 0; j < TT::NQ; j++) {
@@ -951,7 +1211,7 @@ T *dev_at(const Arena &ar, size_t off) {
 }
 
 // One class's tiles: the matrix kernels when `out` is set, the closest kernels otherwise.
-template <int KIND, bool SCALED>
+template <int KIND, bool SCALED, int METRIC>
 int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
   const int count = L.kindCount[KIND];
   if (count == 0) return 0;
@@ -968,24 +1228,32 @@ int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
     const int *tileQ = dev_at<int>(ar, L.oTileQ) + (size_t)tile0 * kTileSlots;
     const int *tileLen = dev_at<int>(ar, L.oTileLen) + (size_t)tile0 * kTileSlots;
     if (out)
-      hipLaunchKernelGGL((ed_matrix_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
+      hipLaunchKernelGGL((ed_matrix_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
                          panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nA, L.nPanels, out);
     else
-      hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
+      hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
                          panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nPanels, dev_at<u64>(ar, L.oBest));
     if (hipGetLastError() != hipSuccess) return -5;
   }
   return 0;
 }
 
-template <bool SCALED>
+template <bool SCALED, int METRIC>
 int launch_all(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
-  int rc = launch_kind<K16, SCALED>(L, ar, out, s);
-  if (rc == 0) rc = launch_kind<K32, SCALED>(L, ar, out, s);
-  if (rc == 0) rc = launch_kind<K64, SCALED>(L, ar, out, s);
-  if (rc == 0) rc = launch_kind<K128, SCALED>(L, ar, out, s);
-  if (rc == 0) rc = launch_kind<K256, SCALED>(L, ar, out, s);
+  int rc = launch_kind<K16, SCALED, METRIC>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K32, SCALED, METRIC>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K64, SCALED, METRIC>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K128, SCALED, METRIC>(L, ar, out, s);
+  if (rc == 0) rc = launch_kind<K256, SCALED, METRIC>(L, ar, out, s);
   return rc;
+}
+
+// The matcher kernels of one request: its metric's, for its code scaling.
+int launch_metric(const Layout &L, const Arena &ar, int metric, int *out, hipStream_t s) {
+  if (metric == METRIC_LEVENSHTEIN)
+    return L.scaled ? launch_all<true, METRIC_LEVENSHTEIN>(L, ar, out, s)
+                    : launch_all<false, METRIC_LEVENSHTEIN>(L, ar, out, s);
+  return L.scaled ? launch_all<true, METRIC_INDEL2>(L, ar, out, s) : launch_all<false, METRIC_INDEL2>(L, ar, out, s);
 }
 
 // The fill kernel of the normalising modes: one lane per panel slot.
@@ -1022,8 +1290,12 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 // panels) or a normalising mode (raw strings in, the device fills the panels
 // under the mode's byte map; the query limit then applies to the normalised
 // query).
+// `metric` is METRIC_INDEL2 (ins = del = 1, sub = 2: the LCS kernels) or
+// METRIC_LEVENSHTEIN (ins = del = sub = 1: the Myers kernels); everything
+// before and after the matcher kernels is the same for both.
 //   step                                 returns
 //   unknown mode                         -9
+//   unknown metric                       -10
 //   no device                            -1
 //   nothing to compute                   0 (closest without options: -1 / -1 per query)
 //   prepare                              -2 query too long, -8 no free byte code, -4 arena
@@ -1035,8 +1307,9 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 //   stream synchronise                   -6 (when nothing failed before)
 // Timings are recorded on success only.
 int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-        int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE) {
+        int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE, int metric = METRIC_INDEL2) {
   if (mode != MODE_NONE && mode != MODE_ALNUM_LOWER) return -9;
+  if (metric != METRIC_INDEL2 && metric != METRIC_LEVENSHTEIN) return -10;
   const bool deviceFill = mode != MODE_NONE;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
@@ -1065,7 +1338,7 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
     rc = launch_fill(L, ar, s);
     (void)hipEventRecord(ar.ev[4], s);
   }
-  if (rc == 0) rc = L.scaled ? launch_all<true>(L, ar, out, s) : launch_all<false>(L, ar, out, s);
+  if (rc == 0) rc = launch_metric(L, ar, metric, out, s);
   (void)hipEventRecord(ar.ev[2], s);
   if (rc == 0) {
     const hipError_t e = outT ? hipMemcpyAsync(outT, out, sizeof(int) * (size_t)nA * nB, hipMemcpyDeviceToHost, s)
@@ -1115,6 +1388,19 @@ int m2k_ed_matrix_norm(const uint8_t *opts, const int64_t *offA, int nA, const u
 int m2k_ed_closest_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB,
                         int nB, int mode, int32_t *bestIdx, int32_t *bestDist) {
   return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode);
+}
+
+// The same two under a metric (0 = ins 1, del 1, sub 2 as above; 1 = unit-cost
+// Levenshtein) and a mode (0 = the strings as they are, 1 = ALNUM_LOWER), in any
+// combination; an unknown metric returns -10.
+int m2k_ed_matrix_metric(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB,
+                         int nB, int mode, int metric, int32_t *outT) {
+  return run(opts, offA, nA, qs, offB, nB, outT, nullptr, nullptr, mode, metric);
+}
+
+int m2k_ed_closest_metric(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB,
+                          int nB, int mode, int metric, int32_t *bestIdx, int32_t *bestDist) {
+  return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode, metric);
 }
 
 // prep / H2D / kernel / D2H milliseconds of the last successful call

@@ -110,11 +110,53 @@ def _use_gpu(pairs, device, queries, normalize=None):
     fits = all(len(q.encode("utf-8", "surrogateescape") if isinstance(q, str) else q) <= limit for q in queries)
     if device == "gpu":
         if not fits:
-            raise gpu.GpuUnavailable("queries longer than %d bytes are not supported on the GPU path" % limit)
+            raise gpu.GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % limit)
         return True
     if not fits or pairs < GPU_MIN_PAIRS or not gpu.gpu_host():
         return False
     return pairs >= GPU_MIN_PAIRS_COLD or _gpu_warm()
+
+
+# costs = (insertion, deletion, substitution).  The GPU kernels serve two
+# triples: the default (1, 1, 2), whose path is untouched by the argument, and
+# (1, 1, 1), plain Levenshtein distance, under the same dispatch rules.  Every
+# other triple is the CPU's scalar DP.
+DEFAULT_COSTS = (1, 1, 2)
+LEVENSHTEIN_COSTS = (1, 1, 1)
+
+
+def _check_costs(costs, device):
+    costs = tuple(costs)
+    if len(costs) != 3 or any(not isinstance(c, int) or c < 0 for c in costs):
+        raise ValueError("costs must be three non-negative integers (insert, delete, substitute), not %r" % (costs,))
+    if costs not in (DEFAULT_COSTS, LEVENSHTEIN_COSTS):
+        if device == "gpu":
+            raise _gpu().GpuUnsupportedInput("the GPU kernels take costs (1, 1, 2) and (1, 1, 1), not %r" % (costs,))
+        device = "cpu"
+    return costs, device
+
+
+def _gpu_kwargs(costs):
+    """Nothing for the default costs: their calls stay as they were."""
+    return {} if costs == DEFAULT_COSTS else {"metric": _gpu().LEVENSHTEIN}
+
+
+def _cpu_matrix(options, queries, costs):
+    na, nb = len(options), len(queries)
+    m = native.module()
+    if m is not None:
+        return m.edit_distance_batch(list(options), list(queries), costs[0], costs[1], costs[2], _threads())
+    np = _np()
+    return np.array([[wagner_fischer_py(o, q, *costs) for q in queries] for o in options],
+                    dtype=np.int32).reshape(na, nb)
+
+
+def _cpu_closest(options, queries, costs):
+    """Other costs than the default: the first minimum of every matrix column."""
+    np = _np()
+    d = _cpu_matrix(options, queries, costs)
+    idx = d.argmin(axis=0).astype(np.int32)
+    return idx, d[idx, np.arange(len(queries))].astype(np.int32)
 
 
 def _threads():
@@ -122,32 +164,34 @@ def _threads():
     return host_threads(16)
 
 
-def matrix(options, queries, device="auto", normalize=None):
+def matrix(options, queries, device="auto", normalize=None, costs=DEFAULT_COSTS):
     """Distance matrix, int32 array of shape [len(options), len(queries)].
 
-    device: "auto" | "cpu" | "gpu"; normalize: None | "alnum_lower"."""
+    device: "auto" | "cpu" | "gpu"; normalize: None | "alnum_lower";
+    costs: (insert, delete, substitute)."""
     _check_normalize(normalize)
+    costs, device = _check_costs(costs, device)
     na, nb = len(options), len(queries)
     if _use_gpu(na * nb, device, queries, normalize):
         gpu = _gpu()
         try:
-            return gpu.ed_matrix_normalized(options, queries) if normalize else gpu.ed_matrix(options, queries)
+            kw = _gpu_kwargs(costs)
+            return (gpu.ed_matrix_normalized(options, queries, **kw) if normalize
+                    else gpu.ed_matrix(options, queries, **kw))
         except gpu.GpuUnsupportedInput:
             if device == "gpu":
                 raise
     options, queries = _normalized(options, normalize), _normalized(queries, normalize)
-    m = native.module()
-    if m is not None:
-        return m.edit_distance_batch(list(options), list(queries), 1, 1, 2, _threads())
-    np = _np()
-    return np.array([[wagner_fischer_py(o, q) for q in queries] for o in options], dtype=np.int32).reshape(na, nb)
+    return _cpu_matrix(options, queries, costs)
 
 
-def closest_indices(options, queries, device="auto", normalize=None):
+def closest_indices(options, queries, device="auto", normalize=None, costs=DEFAULT_COSTS):
     """For every query the index of the first option with the minimum distance
     and that distance (int32 arrays; -1 when there are no options).  The argmin
-    is fused into the distance computation (GPU kernel or native CPU)."""
+    is fused into the distance computation (GPU kernel or native CPU; for costs
+    other than the default the CPU takes it from the matrix)."""
     _check_normalize(normalize)
+    costs, device = _check_costs(costs, device)
     na, nb = len(options), len(queries)
     np = _np()
     if na == 0 or nb == 0:
@@ -155,11 +199,15 @@ def closest_indices(options, queries, device="auto", normalize=None):
     if _use_gpu(na * nb, device, queries, normalize):
         gpu = _gpu()
         try:
-            return gpu.ed_closest_normalized(options, queries) if normalize else gpu.ed_closest(options, queries)
+            kw = _gpu_kwargs(costs)
+            return (gpu.ed_closest_normalized(options, queries, **kw) if normalize
+                    else gpu.ed_closest(options, queries, **kw))
         except gpu.GpuUnsupportedInput:
             if device == "gpu":
                 raise
     options, queries = _normalized(options, normalize), _normalized(queries, normalize)
+    if costs != DEFAULT_COSTS:
+        return _cpu_closest(options, queries, costs)
     m = native.module()
     if m is not None:
         return m.closest_batch(list(options), list(queries), _threads())
@@ -180,17 +228,22 @@ def _closest_py(options, queries):
     return idx, dist
 
 
-def closest_index_list(options, queries, device="auto", normalize=None):
+def closest_index_list(options, queries, device="auto", normalize=None, costs=DEFAULT_COSTS):
     """:func:`closest_indices` as two Python lists.  Below the GPU threshold
-    this path never imports numpy (the native ``closest_list``)."""
+    this path never imports numpy with the default costs (the native
+    ``closest_list``)."""
     _check_normalize(normalize)
+    costs, device = _check_costs(costs, device)
     na, nb = len(options), len(queries)
     if na == 0 or nb == 0:
         return [-1] * nb, [-1] * nb
     if _use_gpu(na * nb, device, queries, normalize):
-        idx, dist = closest_indices(options, queries, device, normalize)
+        idx, dist = closest_indices(options, queries, device, normalize, costs)
         return [int(i) for i in idx], [int(d) for d in dist]
     options, queries = _normalized(options, normalize), _normalized(queries, normalize)
+    if costs != DEFAULT_COSTS:
+        idx, dist = _cpu_closest(options, queries, costs)
+        return [int(i) for i in idx], [int(d) for d in dist]
     m = native.module()
     if m is not None:
         return m.closest_list(list(options), list(queries), _threads())

@@ -88,6 +88,12 @@ def _open_library():
                                             ctypes.c_int, i32p, i32p]
         lib.m2k_ed_last_fill_ms.restype = ctypes.c_double
         lib.m2k_ed_last_fill_ms.argtypes = []
+    if hasattr(lib, "m2k_ed_closest_metric"):   # likewise: the metric entry points
+        lib.m2k_ed_matrix_metric.restype = lib.m2k_ed_closest_metric.restype = ctypes.c_int
+        lib.m2k_ed_matrix_metric.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, i32p]
+        lib.m2k_ed_closest_metric.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p]
     lib.m2k_ed_last_timings.restype = None
     lib.m2k_ed_last_timings.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.m2k_gpu_device_count.restype = ctypes.c_int
@@ -154,9 +160,27 @@ def _lib_or_raise():
     return lib
 
 
-def ed_matrix(options, queries):
+# Metrics of the kernel library (``run()`` in ``ed_kernel.hip``): INDEL2 is
+# ins = del = 1, sub = 2 (the LCS kernels), LEVENSHTEIN is ins = del = sub = 1
+# (the Myers kernels).  Normalising modes: NO_MODE matches the strings as they are.
+INDEL2 = 0
+LEVENSHTEIN = 1
+NO_MODE = 0
+ALNUM_LOWER = 1
+
+
+def _metric_fn(lib, name, metric):
+    if metric not in (INDEL2, LEVENSHTEIN):
+        raise ValueError("unknown metric %r" % (metric,))
+    if not hasattr(lib, name):
+        raise GpuUnavailable("this build of the HIP library has no %s (rebuild it for metric %d)" % (name, metric))
+    return getattr(lib, name)
+
+
+def ed_matrix(options, queries, metric=INDEL2):
     """Distance matrix, shape [len(options), len(queries)] (int32 numpy view of a
-    query-major device result).  Every query must be <= MAX_QUERY_BYTES."""
+    query-major device result).  Every query must be <= MAX_QUERY_BYTES.
+    ``metric``: INDEL2 (the default) or LEVENSHTEIN."""
     lib = _lib_or_raise()
     na, nb = len(options), len(queries)
     if na == 0 or nb == 0:
@@ -166,8 +190,13 @@ def ed_matrix(options, queries):
     if qmax > MAX_QUERY_BYTES:
         raise GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % MAX_QUERY_BYTES)
     outT = np.empty((nb, na), dtype=np.int32)
-    rc = lib.m2k_ed_matrix(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb,
-                           _ptr(outT, ctypes.c_int32))
+    if metric == INDEL2:
+        rc = lib.m2k_ed_matrix(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb,
+                               _ptr(outT, ctypes.c_int32))
+    else:
+        rc = _metric_fn(lib, "m2k_ed_matrix_metric", metric)(
+            a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, NO_MODE, metric,
+            _ptr(outT, ctypes.c_int32))
     if rc in _RC_UNSUPPORTED:
         raise GpuUnsupportedInput("m2k_ed_matrix cannot take this input (code %d)" % rc)
     if rc != 0:
@@ -177,9 +206,10 @@ def ed_matrix(options, queries):
     return outT.T
 
 
-def ed_closest(options, queries):
+def ed_closest(options, queries, metric=INDEL2):
     """(index, distance) int32 arrays: for every query the first option with the
-    minimum distance (-1, -1 when there are no options)."""
+    minimum distance (-1, -1 when there are no options).  ``metric`` as in
+    :func:`ed_matrix`."""
     lib = _lib_or_raise()
     na, nb = len(options), len(queries)
     idx = np.full(nb, -1, dtype=np.int32)
@@ -190,8 +220,13 @@ def ed_closest(options, queries):
     q, offb, qmax = _pack(queries)
     if qmax > MAX_QUERY_BYTES:
         raise GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % MAX_QUERY_BYTES)
-    rc = lib.m2k_ed_closest(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb,
-                            _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    if metric == INDEL2:
+        rc = lib.m2k_ed_closest(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb,
+                                _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    else:
+        rc = _metric_fn(lib, "m2k_ed_closest_metric", metric)(
+            a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, NO_MODE, metric,
+            _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
     if rc in _RC_UNSUPPORTED:
         raise GpuUnsupportedInput("m2k_ed_closest cannot take this input (code %d)" % rc)
     if rc != 0:
@@ -201,11 +236,7 @@ def ed_closest(options, queries):
     return idx, dist
 
 
-# Normalising modes of the kernel library (``run()`` in ``ed_kernel.hip``).
-ALNUM_LOWER = 1
-
-
-def ed_matrix_normalized(options, queries, mode=ALNUM_LOWER):
+def ed_matrix_normalized(options, queries, mode=ALNUM_LOWER, metric=INDEL2):
     """:func:`ed_matrix` of the normalised strings, from the raw ones: keep
     ``0-9 a-z A-Z``, fold to lower case, drop every other byte.  The options are
     normalised on the device as their panels are filled; MAX_QUERY_BYTES applies
@@ -217,13 +248,18 @@ def ed_matrix_normalized(options, queries, mode=ALNUM_LOWER):
     a, offa, _ = _pack(options)
     q, offb, _ = _pack(queries)
     outT = np.empty((nb, na), dtype=np.int32)
-    rc = lib.m2k_ed_matrix_norm(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode,
-                                _ptr(outT, ctypes.c_int32))
+    if metric == INDEL2:
+        rc = lib.m2k_ed_matrix_norm(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode,
+                                    _ptr(outT, ctypes.c_int32))
+    else:
+        rc = _metric_fn(lib, "m2k_ed_matrix_metric", metric)(
+            a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode, metric,
+            _ptr(outT, ctypes.c_int32))
     _check_norm_rc("m2k_ed_matrix_norm", rc)
     return outT.T
 
 
-def ed_closest_normalized(options, queries, mode=ALNUM_LOWER):
+def ed_closest_normalized(options, queries, mode=ALNUM_LOWER, metric=INDEL2):
     """:func:`ed_closest` of the normalised strings, from the raw ones (see
     :func:`ed_matrix_normalized`)."""
     lib = _lib_or_raise()
@@ -234,8 +270,13 @@ def ed_closest_normalized(options, queries, mode=ALNUM_LOWER):
         return idx, dist
     a, offa, _ = _pack(options)
     q, offb, _ = _pack(queries)
-    rc = lib.m2k_ed_closest_norm(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode,
-                                 _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    if metric == INDEL2:
+        rc = lib.m2k_ed_closest_norm(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode,
+                                     _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    else:
+        rc = _metric_fn(lib, "m2k_ed_closest_metric", metric)(
+            a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode, metric,
+            _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
     _check_norm_rc("m2k_ed_closest_norm", rc)
     return idx, dist
 
