@@ -5,7 +5,8 @@ native multi-threaded CPU implementation, on a synthetic "CF foundation"
 
 ``--qmin L --qmax L`` makes every query L bytes, which runs one tile class
 alone (64, 128, 256: K64, K128, K256); ``--lib`` times another build of the
-kernel library, e.g. an earlier commit's, one process per library."""
+kernel library, e.g. an earlier commit's, one process per library;
+``--groups G`` times the closest option per group (see ``bench_groups``)."""
 
 import argparse
 import json
@@ -84,6 +85,67 @@ def bench_raw(a, res):
         raise SystemExit("the two routes disagree: " + json.dumps(res))
 
 
+def bench_groups(a, split):
+    """The closest option per group, two routes from raw names in one process:
+    (a) one ``ed_closest_grouped`` call; (b) one ``ed_closest_normalized`` call
+    per group, which is what a caller without the grouped kernels makes.  The
+    routes alternate after both are warm and their answers are compared.
+    ``split``: "equal" group sizes or "skewed" (sizes ~ 1 / rank)."""
+    import numpy as np
+    rng = random.Random(0)
+    alnum = "abcdefghijklmnopqrstuvwxyz0123456789"
+    opts = raw_names(rng, words(rng, a.options, 4, 40, alnum))
+    qs = raw_names(rng, words(rng, a.queries, min(a.qmin, a.qmax), a.qmax, alnum))
+    G = a.groups
+    weight = np.ones(G) if split == "equal" else 1.0 / np.arange(1, G + 1)
+    ends = np.round(np.cumsum(weight) / weight.sum() * len(opts)).astype(np.int64)
+    sizes = np.diff(np.concatenate(([0], ends)))
+    group_of = np.repeat(np.arange(G, dtype=np.int32), sizes)
+    groups = [opts[e - n:e] for n, e in zip(sizes, ends)]
+    metric = gpu.LEVENSHTEIN if a.costs == "1,1,1" else gpu.INDEL2
+    res = {"groups": G, "split": split, "options": len(opts), "queries": len(qs), "qmin": min(a.qmin, a.qmax),
+           "qmax": a.qmax, "reps": a.reps, "costs": a.costs, "largest_group": int(sizes.max()),
+           "smallest_group": int(sizes.min())}
+
+    def per_group():
+        idx = np.full((len(qs), G), -1, dtype=np.int32)
+        dist = idx.copy()
+        kernel = 0.0
+        for g, (options, first) in enumerate(zip(groups, ends - sizes)):
+            if options:
+                i, dist[:, g] = gpu.ed_closest_normalized(options, qs, metric=metric)
+                idx[:, g] = i + first
+                kernel += gpu.last_timings()["kernel_ms"]
+        return idx, dist, kernel
+
+    gpu.ed_closest_grouped(opts[:1024], group_of[:1024], G, qs[:8], mode=gpu.ALNUM_LOWER, metric=metric)
+    gpu.ed_closest_normalized(opts[:1024], qs[:8], metric=metric)
+    gpu.ed_closest_grouped(opts, group_of, G, qs, mode=gpu.ALNUM_LOWER, metric=metric)   # arena at full size
+    ta, tb, ka, kb, fixed = [], [], [], [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        ra = gpu.ed_closest_grouped(opts, group_of, G, qs, mode=gpu.ALNUM_LOWER, metric=metric)
+        t1 = time.perf_counter()
+        lt = gpu.last_timings()
+        ka.append(lt["kernel_ms"])
+        fixed.append(round((t1 - t0) * 1e3 - lt["kernel_ms"], 3))
+        t2 = time.perf_counter()
+        rb = per_group()
+        t3 = time.perf_counter()
+        kb.append(round(rb[2], 3))
+        ta.append(round((t1 - t0) * 1e3, 3))
+        tb.append(round((t3 - t2) * 1e3, 3))
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    res["routes_agree"] = bool((ra[0] == rb[0]).all() and (ra[1] == rb[1]).all())
+    res.update(grouped_ms=ta, per_group_ms=tb, grouped_kernel_ms=ka, per_group_kernel_ms=kb,
+               grouped_outside_kernel_ms=fixed, grouped_median_ms=med(ta), per_group_median_ms=med(tb),
+               speedup_end_to_end=round(med(tb) / med(ta), 3), kernel_ratio=round(med(ka) / med(kb), 4),
+               arch=gpu.device_arch())
+    print(json.dumps(res), flush=True)
+    if not res["routes_agree"]:
+        raise SystemExit("the two routes disagree")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--options", type=int, default=200000)
@@ -99,10 +161,22 @@ def main():
     ap.add_argument("--costs", default="1,1,2",
                     help="insert,delete,substitute: 1,1,2 (the LCS kernels) or 1,1,1 (the Levenshtein kernels); "
                          "--cpu then times the native scalar DP and takes the first minimum per query")
+    ap.add_argument("--groups", type=int, default=0,
+                    help="split the options into G groups and time one grouped call against G closest calls, from "
+                         "raw names: one JSON line for equal group sizes and one for skewed ones (G = 1: the "
+                         "grouped kernels against the plain closest kernels on the same data)")
     a = ap.parse_args()
     costs = tuple(int(c) for c in a.costs.split(","))
     if costs not in ((1, 1, 2), (1, 1, 1)):
         raise SystemExit("--costs is 1,1,2 or 1,1,1")
+    if a.groups > 0:
+        if a.lib:
+            gpu.LIB_PATH = os.path.abspath(a.lib)
+        if not gpu.available():
+            raise SystemExit("--groups needs the GPU")
+        for split in ("equal", "skewed") if a.groups > 1 else ("equal",):
+            bench_groups(a, split)
+        return
     kw = {"metric": gpu.LEVENSHTEIN} if costs == (1, 1, 1) else {}
     if a.lib:
         gpu.LIB_PATH = os.path.abspath(a.lib)

@@ -175,24 +175,23 @@ def get_buildpack_containerizers(names, options):
     closest buildpack is the closest overall (``getBuildpackContainerizer``).
 
     ``options`` maps builder -> [buildpack ids].  Stage 1 picks, per builder,
-    the buildpack closest to the name; stage 2 picks the closest of those
-    winners (the first builder claiming a buildpack keeps it)."""
+    the buildpack closest to the name, for all builders in one grouped matcher
+    call; stage 2 picks the closest of those winners, which is the first
+    minimum of the stage-1 distances over the builders in sorted order (equal
+    winners have equal distances, so the first builder claiming one keeps it).
+    A builder without buildpacks competes with the empty string, at the
+    distance of the normalised name's length."""
+    from ..ops.editdistance import normalize_alnum_lower
     builders = sorted(options)
     out = []
     if not names:
         return out
-    stage1 = {}
-    for b in builders:
-        stage1[b] = common.get_closest_matching_strings(options[b], names)
+    if not builders:
+        return [collection.BuildpackContainerizer(name, plantypes.CNB, [""]) for name in names]
+    _, dist = common.get_closest_matching_in_groups([options[b] or [] for b in builders], names)
     for j, name in enumerate(names):
-        bpoptions, bps = {}, []
-        for b in builders:
-            opt = stage1[b][j]
-            if opt not in bpoptions:
-                bpoptions[opt] = b
-                bps.append(opt)
-        bp = common.get_closest_matching_string(bps, name)
-        out.append(collection.BuildpackContainerizer(name, plantypes.CNB, [bpoptions.get(bp, "")]))
+        row = [int(d) if d >= 0 else len(normalize_alnum_lower(name)) for d in dist[j]]
+        out.append(collection.BuildpackContainerizer(name, plantypes.CNB, [builders[row.index(min(row))]]))
     return out
 
 

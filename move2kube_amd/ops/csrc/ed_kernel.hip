@@ -122,6 +122,57 @@
 //    K128 0.56, K256 0.53 against the LCS kernels' 0.32 / 0.23 / 0.24 / 0.22 /
 //    0.21 in the same runs: 2.1 to 2.7 times the LCS time per character.  See
 //    docs/history.md.
+//
+// Third family: the closest option of every group (ed_closest_grouped_kernel,
+// both metrics, every class and scaling: 20 kernels).  The matcher's caller has
+// G groups of options (the buildpacks of G builders) and wants the closest one
+// of each group; with the closest kernels that is G requests, each with its own
+// query preparation, copies and launches.  Here the options carry a group id
+// and one pass answers best[q * nGroups + g], the closest kernels' key.
+//  * Order and panels.  The options are sorted by (group, length), stable, and
+//    packed back to back into the same panels of 512: small groups share a
+//    panel, a large group's panels are uniform in group and sorted by length
+//    like today's.  panelBlocks[p] is the maximum over the panel's slots (the
+//    last slot need not be the longest).  One more array is copied,
+//    groupSorted[slot], -1 for an empty slot.  Code map, tables, host and
+//    device fill do not know about groups.
+//  * Reduction.  A lane folds its two options into key[NQ] as in ed_closest;
+//    the wave keeps one held group for those keys, in an SGPR (readlane /
+//    readfirstlane), so every branch on it is scalar.  Per panel and option the
+//    wave ballots its 64 slots' groups:
+//      all live slots in the held group  fold (the only path of a large group:
+//                                        one load, two compares, one s_and)
+//      all in one other group            flush, hold that group, fold
+//      mixed (a boundary in the wave)    every live lane sends its own
+//                                        atomicMin per query; the held stays
+//    A flush is the shuffle min over the wave, one 64-bit atomicMin per query
+//    from lane 0, keys back to ~0; the wave flushes once more after its last
+//    panel.  No LDS stage across the four waves: they may hold different
+//    groups (4 x NQ atomics per workgroup at the end instead of NQ).
+//  * Traps.  The shuffles need all 64 lanes active, so the flush sits in
+//    wave-uniform control flow: the kernel walks the panels itself (over the
+//    shared panel_lcs / panel_lev / query_lcs / query_lev) and takes its
+//    decisions outside the per-lane `live` test; for_each_option calls back
+//    behind `if (o < 0) continue`.  Empty slots (group -1) never fold and never
+//    count as another group.  Ties go to the lowest original index through the
+//    key, whatever order the atomics land in.
+//  * As compiled (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage),
+//    LCS / Levenshtein kernels, the same for SCALED and not, no scratch:
+//             VGPR      SGPR       LDS bytes
+//      K16    58 / 82   106 / 105  4096
+//      K32    50 / 74   70 / 72    4096
+//      K64    48 / 70   54 / 58    4096
+//      K128   60 / 99   58 / 62    8192
+//      K256   62 / 98   50 / 55    8192
+//    (2 to 5 VGPRs over the closest kernels, which costs one resident wave per
+//    SIMD where it crosses a step of 8: LCS K16 7 waves; Levenshtein K16 5,
+//    K32 6, K256 4; the other six keep the closest kernels' count.)  The branches on the ballots and on the held group
+//    compile to s_cbranch_scc / vcc, the held group lives in an SGPR.  The 40
+//    other matcher kernels and ed_fill_panels_kernel keep their figures.
+//  * Measured (200k options x 2048 queries, raw names, MI355X, see
+//    docs/history.md): with one group the kernels take 1.006 times the closest
+//    kernels' time; 8 groups in one call 1.8 times, 64 groups 6 to 7 times
+//    faster end to end than one closest call per group.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -661,6 +712,99 @@ __global__ __launch_bounds__(THREADS) void ed_closest_kernel(
   }
 }
 
+// The closest option of every group (see "Third family" in the file header):
+// best[q * nGroups + g] = min over the options of group g of the closest
+// kernels' key.  The panel walk is this kernel's own, because the reduction
+// needs a hook per (panel, option) that every lane of the wave reaches:
+// for_each_option calls back behind a per-lane skip.
+template <int KIND, bool SCALED, int METRIC>
+__global__ __launch_bounds__(THREADS) void ed_closest_grouped_kernel(
+    const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
+    const int *__restrict__ lenSorted, const int *__restrict__ perm, const int *__restrict__ groupSorted,
+    const uint4 *__restrict__ tileM, const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nPanels,
+    int nGroups, u64 *__restrict__ best) {
+  typedef TileT<KIND> TT;
+  __shared__ uint4 T[TT::TABLE_U4];
+  const int tile = blockIdx.y;
+  load_tile<KIND>(tileM, tile, T);
+  int qlen[TT::NQ], qid[TT::NQ];
+#pragma unroll
+  for (int j = 0; j < TT::NQ; j++) {
+    qlen[j] = tileLen[tile * kTileSlots + j];
+    qid[j] = tileQ[tile * kTileSlots + j];
+  }
+  u64 key[TT::NQ];
+#pragma unroll
+  for (int j = 0; j < TT::NQ; j++) key[j] = ~0ULL;
+  int held = -1;  // the group of what key[] holds, the same for the whole wave; -1 = nothing
+
+  // Runs with all 64 lanes active: min over the wave, one atomic per query, keys back to ~0.
+  auto flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < TT::NQ; j++) {
+      u64 k = key[j];
+      for (int off = 32; off > 0; off >>= 1) {
+        const u64 o = __shfl_xor(k, off, 64);
+        k = o < k ? o : k;
+      }
+      if ((threadIdx.x & 63) == 0 && qid[j] >= 0 && k != ~0ULL) atomicMin(&best[(size_t)qid[j] * nGroups + held], k);
+      key[j] = ~0ULL;
+    }
+  };
+  // Slot s of this lane (empty: group -1), dist(j) = its distance to query j.
+  // Every branch but the innermost `g >= 0` is on a ballot or on `held`: scalar.
+  auto reduce = [&](int s, auto dist) __attribute__((always_inline)) {
+    const int g = groupSorted[s];
+    const u64 live = __builtin_amdgcn_ballot_w64(g >= 0);
+    if (live == 0) return;
+    bool fold = (__builtin_amdgcn_ballot_w64(g != held) & live) == 0;  // every live slot in the held group
+    if (!fold) {
+      const int g0 = __builtin_amdgcn_readlane(g, __builtin_ctzll(live));
+      if ((__builtin_amdgcn_ballot_w64(g != g0) & live) == 0) {  // one other group: it becomes the held one
+        if (held >= 0) flush();
+        held = __builtin_amdgcn_readfirstlane(g0);
+        fold = true;
+      }
+    }
+    if (g < 0) return;
+    const unsigned o = (unsigned)perm[s];
+#pragma unroll
+    for (int j = 0; j < TT::NQ; j++) {
+      const u64 k = ((u64)(unsigned)dist(j) << 32) | o;
+      if (fold)
+        key[j] = k < key[j] ? k : key[j];
+      else if (qid[j] >= 0)  // a group boundary inside these 64 slots: every lane for itself
+        atomicMin(&best[(size_t)qid[j] * nGroups + g], k);
+    }
+  };
+
+  for (int p = remap_panel(blockIdx.x, gridDim.x); p < nPanels; p += gridDim.x) {
+    const int s0 = p * SLOTS + threadIdx.x;
+    if constexpr (METRIC == METRIC_LEVENSHTEIN) {
+      int la[OPT_PER_THREAD];
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) la[u] = lenSorted[s0 + u * THREADS];
+      LevColumn<KIND> C[OPT_PER_THREAD];
+      panel_lev<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), la, C);
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++)
+        reduce(s0 + u * THREADS,
+               [&](int j) __attribute__((always_inline)) { return query_lev<KIND>(C[u], j, qlen[j], la[u]); });
+    } else {
+      typename TT::W V[OPT_PER_THREAD][TT::NW];
+      panel_lcs<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), V);
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) {
+        const int la = lenSorted[s0 + u * THREADS];
+        reduce(s0 + u * THREADS, [&](int j) __attribute__((always_inline)) {
+          return la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
+        });
+      }
+    }
+  }
+  if (held >= 0) flush();
+}
+
 // Panel fill on the device (the normalising mode): raw option bytes in, the
 // panels as [block][slot] 16-byte blocks of stored codes and lenSorted out,
 // under a 256-entry byte map built by the host.  Entry 0 = drop the byte, any
@@ -810,11 +954,14 @@ const int kMaxQueryBytes = TileT<NKINDS - 1>::MAXLEN;
 // tiles in length order, and so are their tables.
 struct Layout {
   int nA = 0, nB = 0, nPanels = 0, scaled = 0;
+  int nGroups = 0;  // > 0: a grouped request (groupSorted is laid out, `best` holds nB * nGroups keys)
   int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
   size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0, oTileQ = 0, oTileLen = 0;
   size_t kindTableOff[NKINDS] = {0, 0, 0, 0, 0};  // the tables of the kind's first tile
   size_t oRaw = 0, oOffA = 0, oByteMap = 0;       // device fill only: its input
+  size_t oGroup = 0;                               // grouped requests only: groupSorted
   size_t h2dBytes = 0, oBest = 0, bytes = 0;
+  size_t nBest() const { return (size_t)nB * (size_t)std::max(nGroups, 1); }
 
   // Byte offset of the mask tables of a tile of `kind`.
   size_t tileTable(int kind, int tile) const {
@@ -939,7 +1086,9 @@ struct PanelPlan {
   std::vector<int64_t> off;
 };
 
-PanelPlan plan_panels(const int64_t *offA, int nA) {
+// With groups (groupOf set, nGroups > 1) the order is (group, length), stable:
+// groups share panels, and a panel's longest option need not be its last.
+PanelPlan plan_panels(const int64_t *offA, int nA, const int32_t *groupOf = nullptr, int nGroups = 0) {
   PanelPlan P;
   // stable counting sort of the options by length
   int maxLen = 0;
@@ -955,14 +1104,23 @@ PanelPlan plan_panels(const int64_t *offA, int nA) {
     std::stable_sort(P.order.begin(), P.order.end(),
                      [&](int x, int y) { return (offA[x + 1] - offA[x]) < (offA[y + 1] - offA[y]); });
   }
+  const bool grouped = groupOf && nGroups > 1;
+  if (grouped) {  // a second stable counting pass, by group, keeps the length order within a group
+    std::vector<int> byLen(P.order), start(nGroups + 1, 0);
+    for (int i = 0; i < nA; i++) start[groupOf[i] + 1]++;
+    for (int g = 0; g < nGroups; g++) start[g + 1] += start[g];
+    for (int i = 0; i < nA; i++) P.order[start[groupOf[byLen[i]]]++] = byLen[i];
+  }
   const int nPanels = (nA + SLOTS - 1) / SLOTS;
   P.blocks.resize(nPanels);
   P.off.resize(nPanels + 1);
   int64_t total = 0;
   for (int p = 0; p < nPanels; p++) {
-    const int last = std::min(nA, (p + 1) * SLOTS) - 1;  // sorted: the panel's longest option
-    const int o = P.order[last];
-    P.blocks[p] = (int)((offA[o + 1] - offA[o] + 15) / 16);
+    const int last = std::min(nA, (p + 1) * SLOTS) - 1;  // sorted by length alone: the panel's longest option
+    int64_t longest = 0;
+    for (int k = grouped ? p * SLOTS : last; k <= last; k++)
+      longest = std::max(longest, offA[P.order[k] + 1] - offA[P.order[k]]);
+    P.blocks[p] = (int)((longest + 15) / 16);
     P.off[p] = total;
     total += (int64_t)P.blocks[p] * SLOTS;
   }
@@ -1028,6 +1186,7 @@ void lay_out(Layout &L, int64_t panelU4, int64_t rawBytes = -1) {
   L.oPanelBlocks = take(sizeof(int) * (size_t)L.nPanels);
   if (!deviceFill) L.oLenSorted = take(lenBytes);
   L.oPerm = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
+  if (L.nGroups > 0) L.oGroup = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
   L.oTileQ = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
   L.oTileLen = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
   for (int k = 0; k < NKINDS; k++) L.kindTableOff[k] = take(kKindTableBytes[k] * (size_t)L.kindCount[k]);
@@ -1041,7 +1200,7 @@ void lay_out(Layout &L, int64_t panelU4, int64_t rawBytes = -1) {
     L.oPanels = take(panelBytes);
     L.oLenSorted = take(lenBytes);
   }
-  L.oBest = take(sizeof(u64) * (size_t)L.nB);
+  L.oBest = take(sizeof(u64) * L.nBest());
   L.bytes = o;
 }
 
@@ -1103,9 +1262,16 @@ void fill_tables(const uint8_t *qs, const int64_t *offB, const uint8_t (&code)[2
   });
 }
 
+// groupSorted[slot] = the group of the slot's option, -1 for an empty slot.
+void fill_groups(const PanelPlan &P, int nA, const int32_t *groupOf, const Layout &L, char *h) {
+  int *groupSorted = reinterpret_cast<int *>(h + L.oGroup);
+  for (int k = 0; k < nA; k++) groupSorted[k] = groupOf[P.order[k]];
+  std::fill(groupSorted + nA, groupSorted + (size_t)L.nPanels * SLOTS, -1);
+}
+
 // Everything up to (not including) the H2D copy.  Returns 0 or an error code.
-int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-            Arena &ar, Layout &L) {
+int prepare(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *groupOf, int nGroups, const uint8_t *qs,
+            const int64_t *offB, int nB, Arena &ar, Layout &L) {
   if (!query_lengths_ok(offB, nB)) return -2;
   const int nt = host_threads();
   uint8_t code[256];
@@ -1117,7 +1283,8 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   uint8_t stored[256];
   for (int b = 0; b < 256; b++) stored[b] = L.scaled ? (uint8_t)(code[b] * 4) : code[b];
 
-  const PanelPlan panels = plan_panels(offA, nA);
+  const PanelPlan panels = plan_panels(offA, nA, groupOf, nGroups);
+  L.nGroups = groupOf ? nGroups : 0;
   L.nPanels = (int)panels.blocks.size();
   const TilePlan tiles = plan_tiles(offB, nB, L.kindStart, L.kindCount);
   L.nTiles = (int)(tiles.q.size() / kTileSlots);
@@ -1127,6 +1294,7 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
   char *h = ar.host;
   memcpy(h + L.oPanelOff, panels.off.data(), sizeof(int64_t) * panels.off.size());
   memcpy(h + L.oPanelBlocks, panels.blocks.data(), sizeof(int) * panels.blocks.size());
+  if (L.nGroups > 0) fill_groups(panels, nA, groupOf, L, h);
   fill_panels(opts, offA, nA, panels, stored, nt, reinterpret_cast<uint4 *>(h + L.oPanels),
               reinterpret_cast<int *>(h + L.oPerm), reinterpret_cast<int *>(h + L.oLenSorted));
   memcpy(h + L.oTileQ, tiles.q.data(), sizeof(int) * tiles.q.size());
@@ -1142,8 +1310,8 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs,
 // and plans the panels on the raw lengths: an upper bound on the normalised
 // ones, the surplus blocks hold code 0.  It reads the option bytes once, to
 // count them, and copies them once.
-int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-                 int mode, Arena &ar, Layout &L) {
+int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *groupOf, int nGroups,
+                 const uint8_t *qs, const int64_t *offB, int nB, int mode, Arena &ar, Layout &L) {
   uint8_t sym[256];
   symbol_table(mode, sym);
   std::vector<uint8_t> nq;
@@ -1167,7 +1335,8 @@ int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t
   L.nB = nB;
   L.scaled = 1;
 
-  const PanelPlan panels = plan_panels(offA, nA);
+  const PanelPlan panels = plan_panels(offA, nA, groupOf, nGroups);
+  L.nGroups = groupOf ? nGroups : 0;
   L.nPanels = (int)panels.blocks.size();
   const TilePlan tiles = plan_tiles(nOffB.data(), nB, L.kindStart, L.kindCount);
   L.nTiles = (int)(tiles.q.size() / kTileSlots);
@@ -1177,6 +1346,7 @@ int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t
   char *h = ar.host;
   memcpy(h + L.oPanelOff, panels.off.data(), sizeof(int64_t) * panels.off.size());
   memcpy(h + L.oPanelBlocks, panels.blocks.data(), sizeof(int) * panels.blocks.size());
+  if (L.nGroups > 0) fill_groups(panels, nA, groupOf, L, h);
   int *perm = reinterpret_cast<int *>(h + L.oPerm);
   memcpy(perm, panels.order.data(), sizeof(int) * (size_t)nA);
   std::fill(perm + nA, perm + (size_t)L.nPanels * SLOTS, -1);
@@ -1210,7 +1380,8 @@ T *dev_at(const Arena &ar, size_t off) {
   return reinterpret_cast<T *>(ar.dev + off);
 }
 
-// One class's tiles: the matrix kernels when `out` is set, the closest kernels otherwise.
+// One class's tiles: the matrix kernels when `out` is set, the grouped closest
+// kernels for a grouped request, the closest kernels otherwise.
 template <int KIND, bool SCALED, int METRIC>
 int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
   const int count = L.kindCount[KIND];
@@ -1230,6 +1401,10 @@ int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
     if (out)
       hipLaunchKernelGGL((ed_matrix_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
                          panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nA, L.nPanels, out);
+    else if (L.nGroups > 0)
+      hipLaunchKernelGGL((ed_closest_grouped_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels,
+                         panelOff, panelBlocks, lenSorted, perm, dev_at<int>(ar, L.oGroup), tileM, tileQ, tileLen,
+                         L.nPanels, L.nGroups, dev_at<u64>(ar, L.oBest));
     else
       hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
                          panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nPanels, dev_at<u64>(ar, L.oBest));
@@ -1285,7 +1460,10 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 }
 
 // One request: the distance matrix into outT when it is set, the closest
-// option per query into bestIdx / bestDist otherwise.
+// option per query into bestIdx / bestDist otherwise; with `groupOf` (the
+// group of every option, nGroups of them) the closest option per query and
+// group, bestIdx / bestDist query-major [nB * nGroups], -1 / -1 for a group
+// without options.
 // `mode` is MODE_NONE (the strings are matched as they are, the host fills the
 // panels) or a normalising mode (raw strings in, the device fills the panels
 // under the mode's byte map; the query limit then applies to the normalised
@@ -1296,6 +1474,8 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 //   step                                 returns
 //   unknown mode                         -9
 //   unknown metric                       -10
+//   groups: nGroups < 1, a group id
+//   outside [0, nGroups)                 -11 (before anything is allocated)
 //   no device                            -1
 //   nothing to compute                   0 (closest without options: -1 / -1 per query)
 //   prepare                              -2 query too long, -8 no free byte code, -4 arena
@@ -1307,23 +1487,30 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 //   stream synchronise                   -6 (when nothing failed before)
 // Timings are recorded on success only.
 int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
-        int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE, int metric = METRIC_INDEL2) {
+        int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE, int metric = METRIC_INDEL2,
+        const int32_t *groupOf = nullptr, int nGroups = 0) {
   if (mode != MODE_NONE && mode != MODE_ALNUM_LOWER) return -9;
   if (metric != METRIC_INDEL2 && metric != METRIC_LEVENSHTEIN) return -10;
+  if (groupOf) {
+    if (nGroups < 1) return -11;
+    for (int i = 0; i < nA; i++)
+      if (groupOf[i] < 0 || groupOf[i] >= nGroups) return -11;
+  }
+  const size_t nBest = (size_t)std::max(nB, 0) * (size_t)(groupOf ? nGroups : 1);
   const bool deviceFill = mode != MODE_NONE;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
   if (nB <= 0 || (outT && nA <= 0)) return 0;
   if (nA <= 0) {
-    for (int j = 0; j < nB; j++) bestIdx[j] = -1, bestDist[j] = -1;
+    for (size_t j = 0; j < nBest; j++) bestIdx[j] = -1, bestDist[j] = -1;
     return 0;
   }
   Arena &ar = arena();
   std::lock_guard<std::mutex> lock(ar.mu);
   const double t0 = now_ms();
   Layout L;
-  int rc = deviceFill ? prepare_norm(opts, offA, nA, qs, offB, nB, mode, ar, L)
-                      : prepare(opts, offA, nA, qs, offB, nB, ar, L);
+  int rc = deviceFill ? prepare_norm(opts, offA, nA, groupOf, nGroups, qs, offB, nB, mode, ar, L)
+                      : prepare(opts, offA, nA, groupOf, nGroups, qs, offB, nB, ar, L);
   if (rc) return rc;
   if (outT && (rc = ar.ensure_out(sizeof(int) * (size_t)nA * nB))) return rc;
   const double prep = now_ms() - t0;
@@ -1331,7 +1518,7 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
   hipStream_t s = ar.stream;
   (void)hipEventRecord(ar.ev[0], s);
   if (hipMemcpyAsync(ar.dev, ar.host, L.h2dBytes, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
-  if (!outT && hipMemsetAsync(best, 0xff, sizeof(u64) * nB, s) != hipSuccess) return -4;
+  if (!outT && hipMemsetAsync(best, 0xff, sizeof(u64) * nBest, s) != hipSuccess) return -4;
   (void)hipEventRecord(ar.ev[1], s);
   int *out = outT ? ar.out : nullptr;
   if (deviceFill) {
@@ -1342,14 +1529,14 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
   (void)hipEventRecord(ar.ev[2], s);
   if (rc == 0) {
     const hipError_t e = outT ? hipMemcpyAsync(outT, out, sizeof(int) * (size_t)nA * nB, hipMemcpyDeviceToHost, s)
-                              : hipMemcpyAsync(hBest, best, sizeof(u64) * nB, hipMemcpyDeviceToHost, s);
+                              : hipMemcpyAsync(hBest, best, sizeof(u64) * nBest, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) rc = -7;
   }
   (void)hipEventRecord(ar.ev[3], s);
   if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = -6;
   if (rc) return rc;
-  if (!outT)
-    for (int j = 0; j < nB; j++) {
+  if (!outT)  // (a key still ~0, a group without options, unpacks to -1 / -1)
+    for (size_t j = 0; j < nBest; j++) {
       bestIdx[j] = (int32_t)(hBest[j] & 0xffffffffULL);
       bestDist[j] = (int32_t)(hBest[j] >> 32);
     }
@@ -1401,6 +1588,20 @@ int m2k_ed_matrix_metric(const uint8_t *opts, const int64_t *offA, int nA, const
 int m2k_ed_closest_metric(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB,
                           int nB, int mode, int metric, int32_t *bestIdx, int32_t *bestDist) {
   return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode, metric);
+}
+
+// Closest option per query and group: groupOf[i] in [0, nGroups) is the group
+// of option i.  bestIdx[j * nGroups + g] = first i of group g minimising
+// dist(opts[i], queries[j]), bestDist the distance, -1 / -1 for a group
+// without options.  Mode and metric as above; a group id out of range or
+// nGroups < 1 returns -11.  With nGroups == 1 the answer is m2k_ed_closest_metric's.
+int m2k_ed_closest_grouped(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *groupOf, int nGroups,
+                           const uint8_t *qs, const int64_t *offB, int nB, int mode, int metric, int32_t *bestIdx,
+                           int32_t *bestDist) {
+  static const int32_t none = 0;  // no options and no group array: still a grouped request
+  if (!groupOf && nA > 0) return -11;
+  return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode, metric, groupOf ? groupOf : &none,
+             nGroups);
 }
 
 // prep / H2D / kernel / D2H milliseconds of the last successful call

@@ -215,6 +215,40 @@ def closest_indices(options, queries, device="auto", normalize=None, costs=DEFAU
     return np.array(idx, dtype=np.int32), np.array(dist, dtype=np.int32)
 
 
+def closest_in_groups(groups, queries, device="auto", normalize=None, costs=DEFAULT_COSTS):
+    """:func:`closest_indices` within every group of options at once.
+
+    ``groups`` is a sequence of option lists.  Returns (idx, dist), int32 arrays
+    of shape [len(queries), len(groups)]: ``idx[j, g]`` is the position within
+    ``groups[g]`` of its first option closest to ``queries[j]``, ``dist[j, g]``
+    the distance, -1 / -1 for an empty group.  On the GPU it is one pass over
+    all options (the grouped kernels); on the CPU one call per group."""
+    _check_normalize(normalize)
+    costs, device = _check_costs(costs, device)
+    np = _np()
+    groups = [list(g) for g in groups]
+    nb, ng = len(queries), len(groups)
+    sizes = [len(g) for g in groups]
+    idx = np.full((nb, ng), -1, dtype=np.int32)
+    dist = np.full((nb, ng), -1, dtype=np.int32)
+    if nb == 0 or sum(sizes) == 0:
+        return idx, dist
+    if _use_gpu(sum(sizes) * nb, device, queries, normalize):
+        gpu = _gpu()
+        try:
+            first = np.cumsum([0] + sizes[:-1]).astype(np.int32)
+            flat, dist = gpu.ed_closest_grouped(
+                [o for g in groups for o in g], np.repeat(np.arange(ng, dtype=np.int32), sizes), ng, queries,
+                mode=gpu.ALNUM_LOWER if normalize else gpu.NO_MODE, **_gpu_kwargs(costs))
+            return np.where(flat < 0, flat, flat - first[None, :]).astype(np.int32), dist
+        except gpu.GpuUnsupportedInput:
+            if device == "gpu":
+                raise
+    for g, options in enumerate(groups):
+        idx[:, g], dist[:, g] = closest_indices(options, queries, "cpu", normalize, costs)
+    return idx, dist
+
+
 def _closest_py(options, queries):
     idx, dist = [], []
     for q in queries:

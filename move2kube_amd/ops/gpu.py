@@ -94,6 +94,11 @@ def _open_library():
                                              ctypes.c_int, ctypes.c_int, i32p]
         lib.m2k_ed_closest_metric.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p]
+    if hasattr(lib, "m2k_ed_closest_grouped"):   # likewise: the closest option per group
+        lib.m2k_ed_closest_grouped.restype = ctypes.c_int
+        lib.m2k_ed_closest_grouped.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, i32p, ctypes.c_int,
+                                               ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               i32p, i32p]
     lib.m2k_ed_last_timings.restype = None
     lib.m2k_ed_last_timings.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.m2k_gpu_device_count.restype = ctypes.c_int
@@ -278,6 +283,37 @@ def ed_closest_normalized(options, queries, mode=ALNUM_LOWER, metric=INDEL2):
             a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, mode, metric,
             _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
     _check_norm_rc("m2k_ed_closest_norm", rc)
+    return idx, dist
+
+
+def ed_closest_grouped(options, group_of, n_groups, queries, mode=NO_MODE, metric=INDEL2):
+    """The closest option of every group: ``group_of[i]`` in ``[0, n_groups)`` is
+    the group of ``options[i]``.  Returns (index, distance) int32 arrays of shape
+    ``[len(queries), n_groups]``; ``index`` is into the flat ``options`` (the
+    first of the group's closest ones), -1 / -1 for a group without options.
+    One pass over the options serves every group.  ``mode``: NO_MODE or
+    ALNUM_LOWER (see :func:`ed_matrix_normalized`); ``metric`` as in :func:`ed_matrix`."""
+    lib = _lib_or_raise()
+    fn = _metric_fn(lib, "m2k_ed_closest_grouped", metric)
+    groups = np.ascontiguousarray(group_of, dtype=np.int32)
+    na, nb = len(options), len(queries)
+    if groups.shape != (na,):
+        raise ValueError("group_of needs one group id per option")
+    if n_groups < 1:
+        raise ValueError("n_groups must be >= 1")
+    idx = np.full((nb, n_groups), -1, dtype=np.int32)
+    dist = np.full((nb, n_groups), -1, dtype=np.int32)
+    if nb == 0 or na == 0:
+        return idx, dist
+    a, offa, _ = _pack(options)
+    q, offb, qmax = _pack(queries)
+    if mode == NO_MODE and qmax > MAX_QUERY_BYTES:
+        raise GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % MAX_QUERY_BYTES)
+    rc = fn(a, _ptr(offa, ctypes.c_int64), na, _ptr(groups, ctypes.c_int32), n_groups, q,
+            _ptr(offb, ctypes.c_int64), nb, mode, metric, _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    if rc == -11:
+        raise ValueError("m2k_ed_closest_grouped: group ids must lie in [0, n_groups)")
+    _check_norm_rc("m2k_ed_closest_grouped", rc)
     return idx, dist
 
 

@@ -882,3 +882,13 @@ def get_closest_matching_strings(options, searches):
         return [""] * len(searches)
     idx, _ = editdistance.closest_index_list(list(options), list(searches), normalize="alnum_lower")
     return [options[i] for i in idx]
+
+
+def get_closest_matching_in_groups(groups, searches):
+    """:func:`get_closest_matching_strings` within every group of options in one
+    pass: (idx, dist) arrays of shape [len(searches), len(groups)], the position
+    in ``groups[g]`` of its closest option and the distance, -1 / -1 for an
+    empty group.  ``dist`` is what :func:`get_closest_matching_string` would
+    compare between the groups' winners."""
+    from ..ops import editdistance
+    return editdistance.closest_in_groups(groups, list(searches), normalize="alnum_lower")
