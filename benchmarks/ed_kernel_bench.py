@@ -6,7 +6,8 @@ native multi-threaded CPU implementation, on a synthetic "CF foundation"
 ``--qmin L --qmax L`` makes every query L bytes, which runs one tile class
 alone (64, 128, 256: K64, K128, K256); ``--lib`` times another build of the
 kernel library, e.g. an earlier commit's, one process per library;
-``--groups G`` times the closest option per group (see ``bench_groups``)."""
+``--groups G`` times the closest option per group (see ``bench_groups``);
+``--topk K`` times the K closest options per query (see ``bench_topk``)."""
 
 import argparse
 import json
@@ -146,6 +147,79 @@ def bench_groups(a, split):
         raise SystemExit("the two routes disagree")
 
 
+def host_topk(d, k):
+    """The first ``k`` of every column of ``d`` in (distance, index) order: a
+    partition per column, ties at the k-th distance taken in index order."""
+    import numpy as np
+    idx = np.full((d.shape[1], k), -1, dtype=np.int32)
+    for j in range(d.shape[1]):
+        col = d[:, j]
+        kth = np.partition(col, k - 1)[k - 1]
+        below = np.flatnonzero(col < kth)
+        cand = np.concatenate((below, np.flatnonzero(col == kth)[:k - len(below)]))
+        idx[j] = cand[np.lexsort((cand, col[cand]))]
+    return idx, np.take_along_axis(d, idx.T, axis=0).T
+
+
+def bench_topk(a):
+    """A ranked list of ``--topk`` options per query, from raw names, three
+    calls alternating in one process after all are warm, every one ending in a
+    stream synchronise: (a) ``ed_closest_k``; (b) ``ed_closest_normalized`` at
+    the same shape (what the selection costs over the plain argmin: compare the
+    kernel times at K = 1); (c) ``ed_matrix_normalized`` plus a partition and
+    sort of every column on the host, the only route to a ranked list without
+    the top-k kernels.  (a) and (c) are checked against each other."""
+    rng = random.Random(0)
+    alnum = "abcdefghijklmnopqrstuvwxyz0123456789"
+    opts = raw_names(rng, words(rng, a.options, 4, 40, alnum))
+    qs = raw_names(rng, words(rng, a.queries, min(a.qmin, a.qmax), a.qmax, alnum))
+    metric = gpu.LEVENSHTEIN if a.costs == "1,1,1" else gpu.INDEL2
+    k = a.topk
+    res = {"topk": k, "options": len(opts), "queries": len(qs), "qmin": min(a.qmin, a.qmax), "qmax": a.qmax,
+           "reps": a.reps, "costs": a.costs}
+    for n in (1024, len(opts)):   # warm, then the arena at full size
+        gpu.ed_closest_k(opts[:n], qs, k, mode=gpu.ALNUM_LOWER, metric=metric)
+        gpu.ed_closest_normalized(opts[:n], qs, metric=metric)
+    host_topk(gpu.ed_matrix_normalized(opts, qs[:8], metric=metric), k)
+    t = {"topk": [], "closest": [], "matrix_host": []}
+    kern = {"topk": [], "closest": [], "matrix_host": []}
+    select, last = [], {}
+
+    def timed(name, fn):
+        t0 = time.perf_counter()
+        r = fn()
+        t1 = time.perf_counter()
+        last[name] = gpu.last_timings()
+        kern[name].append(last[name]["kernel_ms"])
+        return r, t0, t1
+
+    for _ in range(a.reps):
+        ra, t0, t1 = timed("topk", lambda: gpu.ed_closest_k(opts, qs, k, mode=gpu.ALNUM_LOWER, metric=metric))
+        t["topk"].append(round((t1 - t0) * 1e3, 3))
+        rb, t0, t1 = timed("closest", lambda: gpu.ed_closest_normalized(opts, qs, metric=metric))
+        t["closest"].append(round((t1 - t0) * 1e3, 3))
+        if not a.no_matrix:
+            d, t0, t1 = timed("matrix_host", lambda: gpu.ed_matrix_normalized(opts, qs, metric=metric))
+            rc = host_topk(d, k)
+            t2 = time.perf_counter()
+            del d
+            t["matrix_host"].append(round((t2 - t0) * 1e3, 3))
+            select.append(round((t2 - t1) * 1e3, 3))
+    med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+    res["first_rank_is_closest"] = bool((ra[0][:, 0] == rb[0]).all() and (ra[1][:, 0] == rb[1]).all())
+    res.update(topk_ms=t["topk"], closest_ms=t["closest"], topk_kernel_ms=kern["topk"],
+               closest_kernel_ms=kern["closest"], topk_breakdown=last["topk"], closest_breakdown=last["closest"],
+               kernel_ratio_topk_over_closest=round(med(kern["topk"]) / med(kern["closest"]), 4))
+    if not a.no_matrix:
+        res["routes_agree"] = bool((ra[0] == rc[0]).all() and (ra[1] == rc[1]).all())
+        res.update(matrix_host_ms=t["matrix_host"], matrix_kernel_ms=kern["matrix_host"], host_select_ms=select,
+                   speedup_end_to_end=round(med(t["matrix_host"]) / med(t["topk"]), 3))
+    res["arch"] = gpu.device_arch()
+    print(json.dumps(res), flush=True)
+    if not res["first_rank_is_closest"] or not res.get("routes_agree", True):
+        raise SystemExit("the routes disagree")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--options", type=int, default=200000)
@@ -165,10 +239,21 @@ def main():
                     help="split the options into G groups and time one grouped call against G closest calls, from "
                          "raw names: one JSON line for equal group sizes and one for skewed ones (G = 1: the "
                          "grouped kernels against the plain closest kernels on the same data)")
+    ap.add_argument("--topk", type=int, default=0,
+                    help="time the K closest options per query (ed_closest_k) against ed_closest and against "
+                         "ed_matrix plus a host selection, from raw names, alternating (K in 1..64)")
+    ap.add_argument("--no-matrix", action="store_true", help="with --topk: leave the matrix route out")
     a = ap.parse_args()
     costs = tuple(int(c) for c in a.costs.split(","))
     if costs not in ((1, 1, 2), (1, 1, 1)):
         raise SystemExit("--costs is 1,1,2 or 1,1,1")
+    if a.topk > 0:
+        if a.lib:
+            gpu.LIB_PATH = os.path.abspath(a.lib)
+        if not gpu.available():
+            raise SystemExit("--topk needs the GPU")
+        bench_topk(a)
+        return
     if a.groups > 0:
         if a.lib:
             gpu.LIB_PATH = os.path.abspath(a.lib)

@@ -173,6 +173,62 @@
 //    docs/history.md): with one group the kernels take 1.006 times the closest
 //    kernels' time; 8 groups in one call 1.8 times, 64 groups 6 to 7 times
 //    faster end to end than one closest call per group.
+//
+// Fourth family: the k closest options of every query, k <= K_MAX = 64
+// (ed_topk_kernel, both metrics, every class and scaling: 20 kernels, and one
+// ed_topk_merge_kernel).  A ranked list through ed_matrix is nA x nB stores, the
+// copy of the matrix and a host selection per column; the closest kernels'
+// 64-bit atomicMin keeps one key.  Here the selection runs in registers next to
+// the distance work and only k keys per query leave the GPU, in (distance,
+// index) order: the closest kernels' key, so rank 0 is ed_closest's answer.
+//  * Work split, panels, tables, column steps, XCD remap and slabs are the
+//    other families'.  The kernel walks the panels itself like the grouped one:
+//    the selection uses cross-lane operations and sits in wave-uniform control
+//    flow, not behind for_each_option's per-lane skip.
+//  * The list.  Each wave keeps, for every query of the tile, its best 64 keys
+//    as one u64 per lane: lane r holds rank r, ascending, ~0 = no entry (2 VGPRs
+//    per query, 16 for K16).  tau[j] = the key at rank k-1 (v_readlane_b32 x 2),
+//    wave-uniform in SGPRs, ~0 at the start; 0 for an empty query slot, which
+//    then admits nothing.
+//  * Filter.  Per panel and option a lane forms its NQ keys (~0 for an empty
+//    slot), compares each as a full 64-bit key with tau[j] (v_cmp_lt_u64 against
+//    an SGPR pair) and ors the predicates; one ballot per option decides, and
+//    when it is zero - the steady state - nothing else runs.
+//  * Insert (topk_offer / topk_insert).  Otherwise, per query, a scalar loop
+//    over the set bits of that query's ballot: broadcast the lane's key x
+//    (readlane), prev = the list shifted up one lane (v_mov_b32_dpp wave_shr:1,
+//    lane 0 sees 0), l' = l < x ? l : (prev < x ? x : prev), refresh tau[j], and
+//    ballot the remaining candidates against the new tau, so every pass of the
+//    loop inserts.  Keys are distinct (the index is part of them): the order is
+//    total and independent of arrival.  No LDS beyond the mask tables, no
+//    ds_bpermute, no atomics.
+//  * Write-out.  After its last panel a wave stores ranks 0 .. k-1 of every
+//    query, lane r rank r (coalesced), to part[slot][p][rank]: slot = the query's
+//    place in its class (tile * NQ + j), p over the class's gridDim.x * 4 waves.
+//    The partial buffer is device-only (Arena::out, which a matrix request uses
+//    for its output), planned on the host per class (Layout::partOff /
+//    partCount, from grid_x) and cleared to 0xff on the stream before the
+//    launches.  The four waves of a workgroup are not merged in LDS first.
+//  * Merge.  One launch per class, one wave per query slot: it reads the
+//    slot's parts 64 keys at a time (coalesced), filters against its tau and
+//    inserts with the same routine, then writes k keys to best[query][rank],
+//    which the host unpacks like the closest kernels' `best` (~0 = -1 / -1).
+//  * As compiled (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage),
+//    LCS / Levenshtein kernels, the same for SCALED and not, no scratch:
+//             VGPR      SGPR      LDS bytes   waves/SIMD
+//      K16    72 / 96   64 / 58   4096        7 / 5
+//      K32    56 / 80   48 / 44   4096        8 / 6
+//      K64    49 / 72   42 / 44   4096        8 / 7
+//      K128   60 / 99   48 / 50   8192        8 / 4
+//      K256   60 / 96   46 / 50   8192        8 / 5
+//    ed_topk_merge_kernel: 14 VGPRs, 22 SGPRs, no LDS, no scratch.  The loops of
+//    topk_offer branch on s_cmp_lg_u64 / vcc of SGPR values only.  The 61 other
+//    kernels keep their VGPR, SGPR, LDS and scratch figures.
+//  * Measured (200k options x 2048 raw names, MI355X, see docs/history.md):
+//    k = 1 takes 1.03 times the closest kernels' time, k = 8 1.13, k = 64 1.64
+//    (the first panel fills the list by k serial inserts per query and wave,
+//    and K16 has eight queries); against ed_matrix plus a host selection the
+//    call is 58 to 66 times faster end to end.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -805,6 +861,140 @@ __global__ __launch_bounds__(THREADS) void ed_closest_grouped_kernel(
   if (held >= 0) flush();
 }
 
+// The k closest options of every query (see "Fourth family" in the file
+// header).  A wave's list of one query: lane r holds the key of rank r,
+// ascending, ~0 = no entry.  Everything below runs with all 64 lanes active.
+constexpr int K_MAX = 64;  // one rank per lane
+
+__device__ __forceinline__ u64 readlane64(u64 v, int lane) {
+  return ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), lane) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
+}
+
+// Lane r gets lane r-1's value, lane 0 gets 0: v_mov_b32_dpp wave_shr:1 per
+// half, no LDS crossbar.  (0x138 = wave_shr:1; with bound_ctrl off the lane
+// without a source keeps `old`.)
+__device__ __forceinline__ u64 wave_shr1(u64 v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v >> 32), 0x138, 0xf, 0xf, false);
+  return ((u64)hi << 32) | lo;
+}
+
+// The wave-uniform key x goes into the list, the last rank falls out.  Keys
+// are distinct (the option index is part of them), so a lane keeps its entry
+// when it is smaller than x, takes x when its lower neighbour is smaller, and
+// its lower neighbour's entry otherwise.
+__device__ __forceinline__ void topk_insert(u64 &l, u64 x) {
+  const u64 prev = wave_shr1(l);
+  l = l < x ? l : (prev < x ? x : prev);
+}
+
+// Offer the keys of the lanes in `cand` (the ballot of key < tau) to the list:
+// a scalar loop over the set bits.  tau, the key at rank k-1 = km1, is
+// refreshed after every insertion and the remaining candidates are balloted
+// against it again, so every pass of the loop is an insertion: an empty list
+// with k = 1 takes about ln 64 of them from 64 candidates, not 64 tests.
+__device__ __forceinline__ void topk_offer(u64 &l, u64 &tau, u64 key, u64 cand, int km1) {
+  while (cand) {
+    topk_insert(l, readlane64(key, __builtin_ctzll(cand)));
+    tau = readlane64(l, km1);
+    cand &= (cand - 1) & __builtin_amdgcn_ballot_w64(key < tau);
+  }
+}
+
+// Work split and panel walk as in ed_closest_grouped_kernel; wave p of the
+// launch's gridDim.x * 4 (workgroup-major) leaves its ranks 0 .. k-1 of the
+// query in slot j of tile t at part[((t * NQ + j) * P + p) * k + rank], t
+// counted from the launch's first tile.
+template <int KIND, bool SCALED, int METRIC>
+__global__ __launch_bounds__(THREADS) void ed_topk_kernel(
+    const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
+    const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
+    const int *__restrict__ tileQ, const int *__restrict__ tileLen, int nPanels, int k, u64 *__restrict__ part) {
+  typedef TileT<KIND> TT;
+  __shared__ uint4 T[TT::TABLE_U4];
+  const int tile = blockIdx.y;
+  load_tile<KIND>(tileM, tile, T);
+  const int km1 = k - 1;
+  int qlen[TT::NQ];
+  u64 list[TT::NQ], tau[TT::NQ];  // tau[j]: wave-uniform, the key at rank k-1 (an empty query slot admits nothing)
+#pragma unroll
+  for (int j = 0; j < TT::NQ; j++) {
+    qlen[j] = tileLen[tile * kTileSlots + j];
+    list[j] = ~0ULL;
+    tau[j] = tileQ[tile * kTileSlots + j] >= 0 ? ~0ULL : 0ULL;
+  }
+
+  // Slot s of this lane (empty: key ~0, which passes no bound), dist(j) = its
+  // distance to query j.  Every branch is on a ballot or on tau: scalar.
+  auto select = [&](int s, auto dist) __attribute__((always_inline)) {
+    const int o = perm[s];
+    u64 key[TT::NQ];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < TT::NQ; j++) {
+      key[j] = o >= 0 ? ((u64)(unsigned)dist(j) << 32) | (unsigned)o : ~0ULL;
+      any |= key[j] < tau[j];
+    }
+    if (__builtin_amdgcn_ballot_w64(any) == 0) return;  // the steady state
+#pragma unroll
+    for (int j = 0; j < TT::NQ; j++)
+      topk_offer(list[j], tau[j], key[j], __builtin_amdgcn_ballot_w64(key[j] < tau[j]), km1);
+  };
+
+  for (int p = remap_panel(blockIdx.x, gridDim.x); p < nPanels; p += gridDim.x) {
+    const int s0 = p * SLOTS + threadIdx.x;
+    if constexpr (METRIC == METRIC_LEVENSHTEIN) {
+      int la[OPT_PER_THREAD];
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) la[u] = lenSorted[s0 + u * THREADS];
+      LevColumn<KIND> C[OPT_PER_THREAD];
+      panel_lev<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), la, C);
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++)
+        select(s0 + u * THREADS,
+               [&](int j) __attribute__((always_inline)) { return query_lev<KIND>(C[u], j, qlen[j], la[u]); });
+    } else {
+      typename TT::W V[OPT_PER_THREAD][TT::NW];
+      panel_lcs<KIND, SCALED>(panels + panelOff[p], panelBlocks[p], reinterpret_cast<const char *>(T), V);
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) {
+        const int la = lenSorted[s0 + u * THREADS];
+        select(s0 + u * THREADS, [&](int j) __attribute__((always_inline)) {
+          return la + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
+        });
+      }
+    }
+  }
+
+  const int lane = threadIdx.x & 63;
+  const size_t P = (size_t)gridDim.x * (THREADS / 64), p = (size_t)blockIdx.x * (THREADS / 64) + threadIdx.x / 64;
+#pragma unroll
+  for (int j = 0; j < TT::NQ; j++)
+    if (lane < k && tileQ[tile * kTileSlots + j] >= 0) part[(((size_t)tile * TT::NQ + j) * P + p) * k + lane] = list[j];
+}
+
+// One wave per query slot of one class (slot w = tile w / nq, query w % nq of
+// the class's tiles): the P partial lists of k keys each, read 64 keys at a
+// time, go through the same filter and insertion, and ranks 0 .. k-1 land in
+// best[query * k + rank].  A key still ~0 passes no bound.
+__global__ __launch_bounds__(THREADS) void ed_topk_merge_kernel(const u64 *__restrict__ part,
+                                                                const int *__restrict__ tileQ, int nq, int slots,
+                                                                int P, int k, u64 *__restrict__ best) {
+  const int w = blockIdx.x * (THREADS / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+  if (w >= slots) return;  // whole waves leave
+  const int q = tileQ[(w / nq) * kTileSlots + w % nq];
+  if (q < 0) return;
+  const size_t n = (size_t)P * k;
+  const u64 *src = part + (size_t)w * n;
+  u64 list = ~0ULL, tau = ~0ULL;
+  for (size_t at = 0; at < n; at += 64) {
+    const u64 key = at + lane < n ? src[at + lane] : ~0ULL;
+    topk_offer(list, tau, key, __builtin_amdgcn_ballot_w64(key < tau), k - 1);
+  }
+  if (lane < k) best[(size_t)q * k + lane] = list;
+}
+
 // Panel fill on the device (the normalising mode): raw option bytes in, the
 // panels as [block][slot] 16-byte blocks of stored codes and lenSorted out,
 // under a 256-entry byte map built by the host.  Entry 0 = drop the byte, any
@@ -955,13 +1145,18 @@ const int kMaxQueryBytes = TileT<NKINDS - 1>::MAXLEN;
 struct Layout {
   int nA = 0, nB = 0, nPanels = 0, scaled = 0;
   int nGroups = 0;  // > 0: a grouped request (groupSorted is laid out, `best` holds nB * nGroups keys)
+  int k = 0;        // > 0: a top-k request (`best` holds nB * k keys, the part plan below is set)
   int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
   size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0, oTileQ = 0, oTileLen = 0;
   size_t kindTableOff[NKINDS] = {0, 0, 0, 0, 0};  // the tables of the kind's first tile
   size_t oRaw = 0, oOffA = 0, oByteMap = 0;       // device fill only: its input
   size_t oGroup = 0;                               // grouped requests only: groupSorted
   size_t h2dBytes = 0, oBest = 0, bytes = 0;
-  size_t nBest() const { return (size_t)nB * (size_t)std::max(nGroups, 1); }
+  // Top-k only, in u64 keys of the device-only partial buffer (Arena::out): a class's tiles write partCount =
+  // 4 * gridDim.x lists of k keys per query slot, from partOff on, tile-major.
+  size_t partOff[NKINDS] = {0, 0, 0, 0, 0}, partKeys = 0;
+  int partCount[NKINDS] = {0, 0, 0, 0, 0};
+  size_t nBest() const { return (size_t)nB * (size_t)(k > 0 ? k : std::max(nGroups, 1)); }
 
   // Byte offset of the mask tables of a tile of `kind`.
   size_t tileTable(int kind, int tile) const {
@@ -974,7 +1169,7 @@ struct Arena {
   char *host = nullptr;  // pinned staging, same layout as dev
   char *dev = nullptr;
   size_t cap = 0;
-  int *out = nullptr;  // ed_matrix output
+  int *out = nullptr;  // ed_matrix output; the partial lists of a top-k request
   size_t outCap = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1171,6 +1366,8 @@ TilePlan plan_tiles(const int64_t *offB, int nB, int kindStart[NKINDS], int kind
 // the copied range ends with the fill kernel's input (option offsets, byte
 // map, raw bytes; every region 256-byte aligned and a multiple of 256 bytes)
 // and the panels and lenSorted lie behind it.
+int grid_x(int nPanels, int tiles);
+
 void lay_out(Layout &L, int64_t panelU4, int64_t rawBytes = -1) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -1202,6 +1399,13 @@ void lay_out(Layout &L, int64_t panelU4, int64_t rawBytes = -1) {
   }
   L.oBest = take(sizeof(u64) * L.nBest());
   L.bytes = o;
+  if (L.k > 0)  // the part plan: launch_kind gives a class's tiles grid_x workgroups of 4 waves
+    for (int kind = 0; kind < NKINDS; kind++) {
+      if (L.kindCount[kind] == 0) continue;
+      L.partCount[kind] = (THREADS / 64) * grid_x(L.nPanels, L.kindCount[kind]);
+      L.partOff[kind] = L.partKeys;
+      L.partKeys += (size_t)L.kindCount[kind] * kKindQueries[kind] * L.partCount[kind] * L.k;
+    }
 }
 
 // Panels as 16-byte blocks [block][slot] of stored codes, padded with code 0;
@@ -1381,7 +1585,9 @@ T *dev_at(const Arena &ar, size_t off) {
 }
 
 // One class's tiles: the matrix kernels when `out` is set, the grouped closest
-// kernels for a grouped request, the closest kernels otherwise.
+// kernels for a grouped request, the top-k kernels for a top-k request (slab t
+// writes its tiles' partial lists behind those of the slabs before it), the
+// closest kernels otherwise.
 template <int KIND, bool SCALED, int METRIC>
 int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
   const int count = L.kindCount[KIND];
@@ -1405,6 +1611,11 @@ int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
       hipLaunchKernelGGL((ed_closest_grouped_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels,
                          panelOff, panelBlocks, lenSorted, perm, dev_at<int>(ar, L.oGroup), tileM, tileQ, tileLen,
                          L.nPanels, L.nGroups, dev_at<u64>(ar, L.oBest));
+    else if (L.k > 0)
+      hipLaunchKernelGGL((ed_topk_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
+                         panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nPanels, L.k,
+                         reinterpret_cast<u64 *>(ar.out) + L.partOff[KIND] +
+                             (size_t)t * kKindQueries[KIND] * L.partCount[KIND] * L.k);
     else
       hipLaunchKernelGGL((ed_closest_kernel<KIND, SCALED, METRIC>), dim3(gx, rows), dim3(THREADS), 0, s, panels, panelOff,
                          panelBlocks, lenSorted, perm, tileM, tileQ, tileLen, L.nPanels, dev_at<u64>(ar, L.oBest));
@@ -1429,6 +1640,21 @@ int launch_metric(const Layout &L, const Arena &ar, int metric, int *out, hipStr
     return L.scaled ? launch_all<true, METRIC_LEVENSHTEIN>(L, ar, out, s)
                     : launch_all<false, METRIC_LEVENSHTEIN>(L, ar, out, s);
   return L.scaled ? launch_all<true, METRIC_INDEL2>(L, ar, out, s) : launch_all<false, METRIC_INDEL2>(L, ar, out, s);
+}
+
+// The merge of a top-k request: one launch per class, one wave per query slot
+// of the class's tiles, whatever slabs they were launched in.
+int launch_merge(const Layout &L, const Arena &ar, hipStream_t s) {
+  for (int kind = 0; kind < NKINDS; kind++) {
+    if (L.kindCount[kind] == 0) continue;
+    const int slots = L.kindCount[kind] * kKindQueries[kind];
+    hipLaunchKernelGGL(ed_topk_merge_kernel, dim3((slots + THREADS / 64 - 1) / (THREADS / 64)), dim3(THREADS), 0, s,
+                       reinterpret_cast<const u64 *>(ar.out) + L.partOff[kind],
+                       dev_at<const int>(ar, L.oTileQ) + (size_t)L.kindStart[kind] * kTileSlots, kKindQueries[kind],
+                       slots, L.partCount[kind], L.k, dev_at<u64>(ar, L.oBest));
+    if (hipGetLastError() != hipSuccess) return -5;
+  }
+  return 0;
 }
 
 // The fill kernel of the normalising modes: one lane per panel slot.
@@ -1463,7 +1689,11 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 // option per query into bestIdx / bestDist otherwise; with `groupOf` (the
 // group of every option, nGroups of them) the closest option per query and
 // group, bestIdx / bestDist query-major [nB * nGroups], -1 / -1 for a group
-// without options.
+// without options; with `topk` the k closest options per query, bestIdx /
+// bestDist query-major [nB * k] in (distance, index) order, -1 / -1 behind the
+// last option.  Its kernels leave one list per wave in a device-only partial
+// buffer, which ed_topk_merge_kernel folds into `best`; both count as kernel
+// time.
 // `mode` is MODE_NONE (the strings are matched as they are, the host fills the
 // panels) or a normalising mode (raw strings in, the device fills the panels
 // under the mode's byte map; the query limit then applies to the normalised
@@ -1476,19 +1706,22 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 //   unknown metric                       -10
 //   groups: nGroups < 1, a group id
 //   outside [0, nGroups)                 -11 (before anything is allocated)
+//   top-k: k outside [1, K_MAX]          -12 (before anything is allocated)
 //   no device                            -1
 //   nothing to compute                   0 (closest without options: -1 / -1 per query)
 //   prepare                              -2 query too long, -8 no free byte code, -4 arena
-//   matrix: device output buffer         -4
+//   matrix: device output buffer,
+//   top-k: device partial buffer         -4
 //   H2D copy                             -7, at once (no sync)
-//   closest: memset of `best`            -4, at once (no sync)
+//   closest: memset of `best` (top-k:
+//   and of the partial buffer)           -4, at once (no sync)
 //   a kernel launch (the fill included)  -5  } later launches and the D2H copy are
 //   D2H copy                             -7  } skipped, the stream is synchronised
 //   stream synchronise                   -6 (when nothing failed before)
 // Timings are recorded on success only.
 int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
         int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE, int metric = METRIC_INDEL2,
-        const int32_t *groupOf = nullptr, int nGroups = 0) {
+        const int32_t *groupOf = nullptr, int nGroups = 0, bool topk = false, int k = 0) {
   if (mode != MODE_NONE && mode != MODE_ALNUM_LOWER) return -9;
   if (metric != METRIC_INDEL2 && metric != METRIC_LEVENSHTEIN) return -10;
   if (groupOf) {
@@ -1496,7 +1729,8 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
     for (int i = 0; i < nA; i++)
       if (groupOf[i] < 0 || groupOf[i] >= nGroups) return -11;
   }
-  const size_t nBest = (size_t)std::max(nB, 0) * (size_t)(groupOf ? nGroups : 1);
+  if (topk && (k < 1 || k > K_MAX)) return -12;
+  const size_t nBest = (size_t)std::max(nB, 0) * (size_t)(topk ? k : groupOf ? nGroups : 1);
   const bool deviceFill = mode != MODE_NONE;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
@@ -1509,16 +1743,19 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
   std::lock_guard<std::mutex> lock(ar.mu);
   const double t0 = now_ms();
   Layout L;
+  L.k = topk ? k : 0;
   int rc = deviceFill ? prepare_norm(opts, offA, nA, groupOf, nGroups, qs, offB, nB, mode, ar, L)
                       : prepare(opts, offA, nA, groupOf, nGroups, qs, offB, nB, ar, L);
   if (rc) return rc;
   if (outT && (rc = ar.ensure_out(sizeof(int) * (size_t)nA * nB))) return rc;
+  if (topk && (rc = ar.ensure_out(sizeof(u64) * L.partKeys))) return rc;
   const double prep = now_ms() - t0;
   u64 *best = dev_at<u64>(ar, L.oBest), *hBest = reinterpret_cast<u64 *>(ar.host + L.oBest);
   hipStream_t s = ar.stream;
   (void)hipEventRecord(ar.ev[0], s);
   if (hipMemcpyAsync(ar.dev, ar.host, L.h2dBytes, hipMemcpyHostToDevice, s) != hipSuccess) return -7;
   if (!outT && hipMemsetAsync(best, 0xff, sizeof(u64) * nBest, s) != hipSuccess) return -4;
+  if (topk && hipMemsetAsync(ar.out, 0xff, sizeof(u64) * L.partKeys, s) != hipSuccess) return -4;
   (void)hipEventRecord(ar.ev[1], s);
   int *out = outT ? ar.out : nullptr;
   if (deviceFill) {
@@ -1526,6 +1763,7 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
     (void)hipEventRecord(ar.ev[4], s);
   }
   if (rc == 0) rc = launch_metric(L, ar, metric, out, s);
+  if (rc == 0 && topk) rc = launch_merge(L, ar, s);
   (void)hipEventRecord(ar.ev[2], s);
   if (rc == 0) {
     const hipError_t e = outT ? hipMemcpyAsync(outT, out, sizeof(int) * (size_t)nA * nB, hipMemcpyDeviceToHost, s)
@@ -1602,6 +1840,14 @@ int m2k_ed_closest_grouped(const uint8_t *opts, const int64_t *offA, int nA, con
   if (!groupOf && nA > 0) return -11;
   return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode, metric, groupOf ? groupOf : &none,
              nGroups);
+}
+
+// The k closest options per query, k in [1, 64] (-12 otherwise): bestIdx[j * k + r]
+// = the option of rank r in (distance, index) order, so r = 0 is m2k_ed_closest_metric's
+// answer, bestDist its distance, -1 / -1 from rank nA on.  Mode and metric as above.
+int m2k_ed_closest_k(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
+                     int k, int mode, int metric, int32_t *bestIdx, int32_t *bestDist) {
+  return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode, metric, nullptr, 0, true, k);
 }
 
 // prep / H2D / kernel / D2H milliseconds of the last successful call

@@ -249,6 +249,43 @@ def closest_in_groups(groups, queries, device="auto", normalize=None, costs=DEFA
     return idx, dist
 
 
+def closest_k(options, queries, k, device="auto", normalize=None, costs=DEFAULT_COSTS):
+    """The ``k`` closest options of every query, closest first.
+
+    Returns (idx, dist), int32 arrays of shape [len(queries), k]: row ``j`` is
+    the first ``k`` entries of query ``j``'s matrix column in (distance, option
+    index) order, so column 0 is :func:`closest_indices`; -1 / -1 where the
+    options run out.  On the GPU the selection is fused into the distance pass
+    (the top-k kernels, ``k`` up to ``gpu.MAX_K``); the CPU sorts the matrix."""
+    _check_normalize(normalize)
+    costs, device = _check_costs(costs, device)
+    if k < 1:
+        raise ValueError("k must be >= 1, not %r" % (k,))
+    np = _np()
+    na, nb = len(options), len(queries)
+    idx = np.full((nb, k), -1, dtype=np.int32)
+    dist = np.full((nb, k), -1, dtype=np.int32)
+    if na == 0 or nb == 0:
+        return idx, dist
+    if k > _gpu().MAX_K:
+        if device == "gpu":
+            raise _gpu().GpuUnsupportedInput("the GPU path ranks at most %d options per query" % _gpu().MAX_K)
+        device = "cpu"
+    if _use_gpu(na * nb, device, queries, normalize):
+        gpu = _gpu()
+        try:
+            return gpu.ed_closest_k(options, queries, k, mode=gpu.ALNUM_LOWER if normalize else gpu.NO_MODE,
+                                    **_gpu_kwargs(costs))
+        except gpu.GpuUnsupportedInput:
+            if device == "gpu":
+                raise
+    d = _cpu_matrix(_normalized(options, normalize), _normalized(queries, normalize), costs)
+    order = np.argsort(d, axis=0, kind="stable")[:k]
+    idx[:, :len(order)] = order.T
+    dist[:, :len(order)] = np.take_along_axis(d, order, axis=0).T
+    return idx, dist
+
+
 def _closest_py(options, queries):
     idx, dist = [], []
     for q in queries:

@@ -29,8 +29,12 @@ class GpuUnavailable(RuntimeError):
 MAX_QUERY_BYTES = 256
 
 
+# Longest ranked list of the top-k kernels: a wave keeps one rank per lane.
+MAX_K = 64
+
+
 class GpuUnsupportedInput(GpuUnavailable):
-    """The kernel cannot take this input (query > MAX_QUERY_BYTES, all 256 byte values used)."""
+    """The kernel cannot take this input (query > MAX_QUERY_BYTES, all 256 byte values used, k > MAX_K)."""
 
 
 _RC_UNSUPPORTED = (-2, -8)
@@ -99,6 +103,10 @@ def _open_library():
         lib.m2k_ed_closest_grouped.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, i32p, ctypes.c_int,
                                                ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                i32p, i32p]
+    if hasattr(lib, "m2k_ed_closest_k"):   # likewise: the k closest options
+        lib.m2k_ed_closest_k.restype = ctypes.c_int
+        lib.m2k_ed_closest_k.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p]
     lib.m2k_ed_last_timings.restype = None
     lib.m2k_ed_last_timings.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.m2k_gpu_device_count.restype = ctypes.c_int
@@ -314,6 +322,33 @@ def ed_closest_grouped(options, group_of, n_groups, queries, mode=NO_MODE, metri
     if rc == -11:
         raise ValueError("m2k_ed_closest_grouped: group ids must lie in [0, n_groups)")
     _check_norm_rc("m2k_ed_closest_grouped", rc)
+    return idx, dist
+
+
+def ed_closest_k(options, queries, k, mode=NO_MODE, metric=INDEL2):
+    """The ``k`` closest options of every query: (index, distance) int32 arrays of
+    shape ``[len(queries), k]``, row ``j`` in (distance, option index) order, so
+    column 0 is :func:`ed_closest`'s answer; -1 / -1 behind the last option.
+    ``k`` is at most MAX_K.  The selection runs on the device (one sorted list
+    per wave, then a merge): only ``k`` pairs per query come back.  ``mode`` and
+    ``metric`` as in :func:`ed_closest_grouped`."""
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if k > MAX_K:
+        raise GpuUnsupportedInput("the GPU path ranks at most %d options per query" % MAX_K)
+    fn = _metric_fn(_lib_or_raise(), "m2k_ed_closest_k", metric)
+    na, nb = len(options), len(queries)
+    idx = np.full((nb, k), -1, dtype=np.int32)
+    dist = np.full((nb, k), -1, dtype=np.int32)
+    if nb == 0 or na == 0:
+        return idx, dist
+    a, offa, _ = _pack(options)
+    q, offb, qmax = _pack(queries)
+    if mode == NO_MODE and qmax > MAX_QUERY_BYTES:
+        raise GpuUnsupportedInput("queries longer than %d bytes are not supported on the GPU path" % MAX_QUERY_BYTES)
+    rc = fn(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, k, mode, metric,
+            _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
+    _check_norm_rc("m2k_ed_closest_k", rc)
     return idx, dist
 
 

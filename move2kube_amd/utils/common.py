@@ -884,6 +884,15 @@ def get_closest_matching_strings(options, searches):
     return [options[i] for i in idx]
 
 
+def get_k_closest_matching_strings(options, searches, k):
+    """The ``k`` options closest to every search string, closest first (ties in
+    the options' order): a list of lists, shorter than ``k`` when the options
+    run out.  Its first entries are :func:`get_closest_matching_strings`."""
+    from ..ops import editdistance
+    idx, _ = editdistance.closest_k(list(options), list(searches), k, normalize="alnum_lower")
+    return [[options[i] for i in row if i >= 0] for row in idx.tolist()]
+
+
 def get_closest_matching_in_groups(groups, searches):
     """:func:`get_closest_matching_strings` within every group of options in one
     pass: (idx, dist) arrays of shape [len(searches), len(groups)], the position
