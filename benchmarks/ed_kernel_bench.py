@@ -7,7 +7,9 @@ native multi-threaded CPU implementation, on a synthetic "CF foundation"
 alone (64, 128, 256: K64, K128, K256); ``--lib`` times another build of the
 kernel library, e.g. an earlier commit's, one process per library;
 ``--groups G`` times the closest option per group (see ``bench_groups``);
-``--topk K`` times the K closest options per query (see ``bench_topk``)."""
+``--topk K`` times the K closest options per query (see ``bench_topk``);
+``--names-route on`` times a few options against very many names (see
+``bench_names``)."""
 
 import argparse
 import json
@@ -220,6 +222,79 @@ def bench_topk(a):
         raise SystemExit("the routes disagree")
 
 
+def bench_names(a):
+    """Few options against very many raw names (``--options`` small, ``--queries``
+    large), two routes alternating in one process after both are warm:
+    (a) ``ed_closest_names``, the names in the lanes; (b) today's route on the
+    same inputs, ``ed_closest_grouped`` with ``--groups`` > 0 and
+    ``ed_closest_normalized`` without; and (c) the public function on them,
+    ``editdistance.closest_in_groups`` / ``closest_indices`` with ``device="gpu"``,
+    which adds its checks of the input and takes whichever route its rule names
+    (``public_takes_names_route``).  ``--names-route off`` times (b) alone.
+    Every repetition's answers are compared.  The names are drawn from 50k
+    distinct ones, as a foundation export repeats its buildpack names."""
+    import numpy as np
+    from move2kube_amd.ops import editdistance as ed
+    rng = random.Random(0)
+    alnum = "abcdefghijklmnopqrstuvwxyz0123456789"
+    opts = raw_names(rng, words(rng, a.options, 4, 40, alnum))
+    distinct = raw_names(rng, words(rng, min(a.queries, 50000), min(a.qmin, a.qmax), a.qmax, alnum))
+    qs = rng.choices(distinct, k=a.queries)
+    G = a.groups
+    group_of = [i * G // len(opts) for i in range(len(opts))] if G > 0 else None
+    metric = gpu.LEVENSHTEIN if a.costs == "1,1,1" else gpu.INDEL2
+    on = a.names_route == "on"
+    res = {"names_route": a.names_route, "options": len(opts), "groups": G, "queries": len(qs),
+           "qmin": min(a.qmin, a.qmax), "qmax": a.qmax, "reps": a.reps, "costs": a.costs}
+
+    def names():
+        return gpu.ed_closest_names(opts, qs, group_of, max(G, 1), mode=gpu.ALNUM_LOWER, metric=metric)
+
+    def existing():
+        if G > 0:
+            return gpu.ed_closest_grouped(opts, group_of, G, qs, mode=gpu.ALNUM_LOWER, metric=metric)
+        return gpu.ed_closest_normalized(opts, qs, metric=metric)
+
+    costs = tuple(int(c) for c in a.costs.split(","))
+    groups = [[o for o, g in zip(opts, group_of) if g == at] for at in range(G)] if G > 0 else None
+    first = np.cumsum([0] + [len(g) for g in groups[:-1]]).astype(np.int32) if G > 0 else None
+
+    def public():
+        if G > 0:
+            return ed.closest_in_groups(groups, qs, device="gpu", normalize="alnum_lower", costs=costs)
+        return ed.closest_indices(opts, qs, device="gpu", normalize="alnum_lower", costs=costs)
+
+    routes = ([("names", names)] if on else []) + [("existing", existing)] + ([("public", public)] if on else [])
+    for _, fn in routes:   # warm: context, then the arena at full size
+        fn()
+    t = {name: [] for name, _ in routes}
+    kern = {name: [] for name, _ in routes}
+    last, agree = {}, True
+    for _ in range(a.reps):
+        got = {}
+        for name, fn in routes:
+            t0 = time.perf_counter()
+            got[name] = fn()
+            t[name].append(round((time.perf_counter() - t0) * 1e3, 3))
+            last[name] = gpu.last_timings()
+            kern[name].append(last[name]["kernel_ms"])
+        if on:
+            if G > 0:   # positions within the groups to indices into the flat options
+                got["public"] = (np.where(got["public"][0] < 0, -1, got["public"][0] + first), got["public"][1])
+            agree = agree and all((x == y).all() and (x == z).all()
+                                  for x, y, z in zip(got["names"], got["existing"], got["public"]))
+    for name, _ in routes:
+        res[name + "_ms"], res[name + "_kernel_ms"], res[name + "_breakdown"] = t[name], kern[name], last[name]
+    if on:
+        res["routes_agree"] = bool(agree)
+        res["names_wholly_below_existing"] = max(t["names"]) < min(t["existing"])
+        res["public_takes_names_route"] = ed.names_route(len(opts), len(qs))
+    res["arch"] = gpu.device_arch()
+    print(json.dumps(res), flush=True)
+    if not agree:
+        raise SystemExit("the routes disagree")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--options", type=int, default=200000)
@@ -243,10 +318,21 @@ def main():
                     help="time the K closest options per query (ed_closest_k) against ed_closest and against "
                          "ed_matrix plus a host selection, from raw names, alternating (K in 1..64)")
     ap.add_argument("--no-matrix", action="store_true", help="with --topk: leave the matrix route out")
+    ap.add_argument("--names-route", choices=("off", "on"), default=None,
+                    help="few options against many raw names (small --options, large --queries; --groups G for the "
+                         "grouped request): on = ed_closest_names alternating with today's route, off = today's "
+                         "route alone (see bench_names)")
     a = ap.parse_args()
     costs = tuple(int(c) for c in a.costs.split(","))
     if costs not in ((1, 1, 2), (1, 1, 1)):
         raise SystemExit("--costs is 1,1,2 or 1,1,1")
+    if a.names_route:
+        if a.lib:
+            gpu.LIB_PATH = os.path.abspath(a.lib)
+        if not gpu.available():
+            raise SystemExit("--names-route needs the GPU")
+        bench_names(a)
+        return
     if a.topk > 0:
         if a.lib:
             gpu.LIB_PATH = os.path.abspath(a.lib)

@@ -229,6 +229,74 @@
 //    (the first panel fills the list by k serial inserts per query and wave,
 //    and K16 has eight queries); against ed_matrix plus a host selection the
 //    call is 58 to 66 times faster end to end.
+//
+// Fifth family: many names against a few options (ed_closest_names_kernel,
+// both metrics, every class and scaling: 20 kernels; an ungrouped request is a
+// grouped one with one group).  The four families above put the options in the
+// lanes and the queries' tables in LDS; with a few dozen options that is one
+// panel with most lanes empty, and a table staged per 8 queries.  Both metrics
+// have ins = del, so dist(a, b) = dist(b, a) and the roles can be swapped: here
+// the names are the panel side (sorted by length, 512 to a panel, two per lane,
+// host or device fill as before) and the options the tile side.  The 256-byte
+// limit moves to the options with the column; a name can be of any length.
+// Reused as they are: panel_lcs / panel_lev / query_lcs / query_lev, the code
+// map (ranked by the names' bytes, the side the lanes look up), the tables and
+// the [block][slot] panels.  This family's own:
+//  * Tile plan (plan_tiles_grouped).  Options ordered by (class, group, length),
+//    stable; a tile is closed on a change of class or group and its remaining
+//    slots stay empty, so a tile never holds two groups.  One more array,
+//    tileGroup[t], is copied with tileQ / tileLen.
+//  * Work split.  The grid is over panels only: one launch per class that has
+//    tiles, no blockIdx.y.  A workgroup takes a panel (up to 4096 panels one
+//    each, beyond that persistent and strided, XCD remap as above) and loops
+//    over the class's tiles inside the kernel, so a lane's running minimum per
+//    name never leaves its registers.  The tile index, tileGroup, tileQ /
+//    tileLen and the held group come from kernel arguments and uniform loads:
+//    SGPRs, scalar branches.
+//  * LDS.  kNamesChunkBytes = 32 KiB of tables are resident at once, static: 8
+//    tiles of the classes up to 64 bytes (64 / 32 / 16 options), 4 of the wide
+//    ones (8 / 4 options).  A class that fits one chunk - a few dozen options,
+//    the expected case - is staged once per workgroup before the panel loop,
+//    otherwise per (panel, chunk) between two barriers (8 uint4 loads per lane
+//    against 2 names x ~25 characters x 8 tiles x NSUB ds_read_b64: a few per
+//    cent).  gfx950 has 160 KiB of LDS per CU (the compiler's occupancy figure
+//    below is 160 / 32 = 5), so 32 KiB leaves 5 resident workgroups of 4 waves
+//    = 5 waves per SIMD: what the Levenshtein kernels' VGPRs allow anyway (4 to
+//    5), and 3 below the 8 the LCS kernels' 62 to 80 VGPRs would.  16 KiB would
+//    keep all 8 but puts the collector's grouped shape (8 groups: 8 tiles per
+//    class) on the per-panel path; above 64 KiB needs dynamic LDS and larger
+//    workgroups for 2 resident ones.  Not measured against each other.  The
+//    ds_read_b64 scheme and the empty-asm barrier are step4's / lev_char's; a
+//    tile's base is one more scalar term of the address.
+//  * Names are read again for every tile (the panel is L1 / L2 resident after
+//    the first).  Holding short names' blocks in registers across tiles was not
+//    built.
+//  * Reduction.  None across lanes: no shuffles, no LDS stage, no ballots.  A
+//    lane folds a tile's NQ distances into key = (dist << 32 | original option
+//    index) of the held group (ties to the lowest index whatever the tile
+//    order), and when tileGroup changes, and after the last tile, commits it
+//    to best[name * nGroups + group] (preset to ~0) by a plain load / min /
+//    store: one lane of one workgroup owns the entry within a launch, and the
+//    class launches of a request are ordered on its stream, so no atomic is
+//    needed.  Empty tile slots and empty panel slots contribute nothing.
+//  * As compiled (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage),
+//    LCS / Levenshtein kernels, the same for SCALED and not, no scratch:
+//             VGPR       SGPR      LDS bytes   waves/SIMD
+//      K16    62 / 76    60 / 63   32768       5 / 5
+//      K32    62 / 77    60 / 62   32768       5 / 5
+//      K64    63 / 78    60 / 62   32768       5 / 5
+//      K128   76 / 107   61 / 62   32768       5 / 4
+//      K256   80 / 109   61 / 62   32768       5 / 4
+//    The 82 other kernels keep their VGPR, SGPR, LDS and scratch figures.
+//  * Measured (1M raw names, 4 to 64 bytes, MI355X, see docs/history.md): 64
+//    options, kernel time 0.48 ms against the closest kernels' 3.1 to 3.2 ms
+//    (8 groups: 0.82 against the grouped kernels' 3.6; Levenshtein 1.02 against
+//    2.26 and 1.51 against 3.10); end to end 24 to 36 ms against 157 to 176 ms,
+//    because the host no longer builds a table per 2 to 8 names.  At 1M names
+//    the kernel times meet at 1024 options (ungrouped) and stay level to 4096.
+//    Over the name count they meet near 1024 names per option; with few names
+//    the grid is a handful of workgroups and the other families' kernels are
+//    faster.  The raw lines are in profiles/ed_names/.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -995,6 +1063,108 @@ __global__ __launch_bounds__(THREADS) void ed_topk_merge_kernel(const u64 *__res
   if (lane < k) best[(size_t)q * k + lane] = list;
 }
 
+// Many names against a few options (see "Fifth family" in the file header): the
+// names sit in the panels, two to a lane, the options in the tiles.  The grid
+// is over panels only; a workgroup walks the launch's tiles (one class, ordered
+// by group) for every panel of its own, kNamesChunkBytes of tables resident in
+// LDS at a time, and a lane keeps its two names' running minima in registers:
+//   best[name * nGroups + g] = min over the options of group g of
+//                              (dist << 32 | original option index)
+// `t`, tileGroup[t], tileQ / tileLen[t] and `held` depend on kernel arguments
+// and uniform loads only: they live in SGPRs and every branch on them is scalar.
+constexpr int kNamesChunkBytes = 32 * 1024;
+
+template <int KIND, bool SCALED, int METRIC>
+__global__ __launch_bounds__(THREADS) void ed_closest_names_kernel(
+    const uint4 *__restrict__ panels, const int64_t *__restrict__ panelOff, const int *__restrict__ panelBlocks,
+    const int *__restrict__ lenSorted, const int *__restrict__ perm, const uint4 *__restrict__ tileM,
+    const int *__restrict__ tileQ, const int *__restrict__ tileLen, const int *__restrict__ tileGroup, int nTiles,
+    int nPanels, int nGroups, u64 *best) {
+  typedef TileT<KIND> TT;
+  constexpr int CHUNK = kNamesChunkBytes / TT::TABLE_BYTES;  // tiles resident at once: 8, the wide classes 4
+  __shared__ uint4 T[CHUNK * TT::TABLE_U4];
+  // Tables of tiles [first, first + n) of the launch into T, n <= CHUNK.
+  auto stage = [&](int first, int n) __attribute__((always_inline)) {
+    const uint4 *src = tileM + (size_t)first * TT::TABLE_U4;
+    for (int i = threadIdx.x; i < n * TT::TABLE_U4; i += THREADS) T[i] = src[i];
+    __syncthreads();
+  };
+  const bool resident = nTiles <= CHUNK;  // the expected case: staged once, before the panel walk
+  if (resident) stage(0, nTiles);
+
+  for (int p = remap_panel(blockIdx.x, gridDim.x); p < nPanels; p += gridDim.x) {
+    const int s0 = p * SLOTS + threadIdx.x;
+    int la[OPT_PER_THREAD], name[OPT_PER_THREAD];  // an empty slot: length 0, name -1, it commits nothing
+    u64 key[OPT_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < OPT_PER_THREAD; u++) {
+      la[u] = lenSorted[s0 + u * THREADS];
+      name[u] = perm[s0 + u * THREADS];
+      key[u] = ~0ULL;
+    }
+    const uint4 *panel = panels + panelOff[p];
+    const int blocks = panelBlocks[p];
+    int held = -1;  // the group of what key[] holds; -1 = nothing
+    // One lane of one workgroup owns best[name][*], and the launches of a
+    // request are ordered on its stream: a plain load / min / store.
+    auto commit = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < OPT_PER_THREAD; u++) {
+        if (name[u] >= 0 && key[u] != ~0ULL) {
+          u64 *b = best + (size_t)name[u] * nGroups + held;
+          if (key[u] < *b) *b = key[u];
+        }
+        key[u] = ~0ULL;
+      }
+    };
+
+    for (int c0 = 0; c0 < nTiles; c0 += CHUNK) {
+      const int n = nTiles - c0 < CHUNK ? nTiles - c0 : CHUNK;
+      if (!resident) {
+        __syncthreads();  // every wave is done with the chunk before
+        stage(c0, n);
+      }
+      for (int i = 0; i < n; i++) {
+        const int t = c0 + i;
+        const int g = tileGroup[t];
+        if (g != held) {
+          if (held >= 0) commit();
+          held = g;
+        }
+        const char *Tt = reinterpret_cast<const char *>(T) + i * TT::TABLE_BYTES;
+        const int *qid = tileQ + t * kTileSlots, *qlen = tileLen + t * kTileSlots;
+        if constexpr (METRIC == METRIC_LEVENSHTEIN) {
+          LevColumn<KIND> C[OPT_PER_THREAD];
+          panel_lev<KIND, SCALED>(panel, blocks, Tt, la, C);
+#pragma unroll
+          for (int j = 0; j < TT::NQ; j++) {
+            if (qid[j] < 0) continue;
+#pragma unroll
+            for (int u = 0; u < OPT_PER_THREAD; u++) {
+              const u64 k = ((u64)(unsigned)query_lev<KIND>(C[u], j, qlen[j], la[u]) << 32) | (unsigned)qid[j];
+              key[u] = k < key[u] ? k : key[u];
+            }
+          }
+        } else {
+          typename TT::W V[OPT_PER_THREAD][TT::NW];
+          panel_lcs<KIND, SCALED>(panel, blocks, Tt, V);
+#pragma unroll
+          for (int j = 0; j < TT::NQ; j++) {
+            if (qid[j] < 0) continue;
+#pragma unroll
+            for (int u = 0; u < OPT_PER_THREAD; u++) {
+              const int d = la[u] + qlen[j] - 2 * query_lcs<KIND>(V[u], j, qlen[j]);
+              const u64 k = ((u64)(unsigned)d << 32) | (unsigned)qid[j];
+              key[u] = k < key[u] ? k : key[u];
+            }
+          }
+        }
+      }
+    }
+    if (held >= 0) commit();
+  }
+}
+
 // Panel fill on the device (the normalising mode): raw option bytes in, the
 // panels as [block][slot] 16-byte blocks of stored codes and lenSorted out,
 // under a 256-entry byte map built by the host.  Entry 0 = drop the byte, any
@@ -1146,17 +1316,20 @@ struct Layout {
   int nA = 0, nB = 0, nPanels = 0, scaled = 0;
   int nGroups = 0;  // > 0: a grouped request (groupSorted is laid out, `best` holds nB * nGroups keys)
   int k = 0;        // > 0: a top-k request (`best` holds nB * k keys, the part plan below is set)
+  int names = 0;    // the names route: nA names in the panels, nB options in the tiles, grouped by tileGroup
+                    // (nGroups >= 1, no groupSorted), `best` holds nA * nGroups keys
   int nTiles = 0, kindStart[NKINDS] = {0, 0, 0, 0, 0}, kindCount[NKINDS] = {0, 0, 0, 0, 0};
   size_t oPanels = 0, oPanelOff = 0, oPanelBlocks = 0, oLenSorted = 0, oPerm = 0, oTileQ = 0, oTileLen = 0;
   size_t kindTableOff[NKINDS] = {0, 0, 0, 0, 0};  // the tables of the kind's first tile
   size_t oRaw = 0, oOffA = 0, oByteMap = 0;       // device fill only: its input
   size_t oGroup = 0;                               // grouped requests only: groupSorted
+  size_t oTileGroup = 0;                           // names route only: tileGroup
   size_t h2dBytes = 0, oBest = 0, bytes = 0;
   // Top-k only, in u64 keys of the device-only partial buffer (Arena::out): a class's tiles write partCount =
   // 4 * gridDim.x lists of k keys per query slot, from partOff on, tile-major.
   size_t partOff[NKINDS] = {0, 0, 0, 0, 0}, partKeys = 0;
   int partCount[NKINDS] = {0, 0, 0, 0, 0};
-  size_t nBest() const { return (size_t)nB * (size_t)(k > 0 ? k : std::max(nGroups, 1)); }
+  size_t nBest() const { return names ? (size_t)nA * nGroups : (size_t)nB * (size_t)(k > 0 ? k : std::max(nGroups, 1)); }
 
   // Byte offset of the mask tables of a tile of `kind`.
   size_t tileTable(int kind, int tile) const {
@@ -1328,6 +1501,7 @@ PanelPlan plan_panels(const int64_t *offA, int nA, const int32_t *groupOf = null
 // (kTileSlots per tile); kindStart / kindCount get each class's run of tiles.
 struct TilePlan {
   std::vector<int> q, len;
+  std::vector<int> group;  // names route only: tileGroup[t]
 };
 
 TilePlan plan_tiles(const int64_t *offB, int nB, int kindStart[NKINDS], int kindCount[NKINDS]) {
@@ -1360,6 +1534,48 @@ TilePlan plan_tiles(const int64_t *offB, int nB, int kindStart[NKINDS], int kind
   return P;
 }
 
+// The names route's tiles: the options (the tile side there) ordered by (class,
+// group, length), stable, so a class's tiles are one run and a group's tiles
+// one run within it.  A tile never holds two groups: it is closed on a change
+// of class or group and its remaining slots stay empty (-1, length 0).
+// groupOf == nullptr: one group.
+TilePlan plan_tiles_grouped(const int64_t *offB, int nB, const int32_t *groupOf, int kindStart[NKINDS],
+                            int kindCount[NKINDS]) {
+  auto length = [&](int j) { return (int)(offB[j + 1] - offB[j]); };
+  auto kindOf = [&](int j) {
+    int kind = K16;
+    while (length(j) > kKindMaxLen[kind]) kind++;
+    return kind;
+  };
+  std::vector<int> order(nB);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+    const int kx = kindOf(x), ky = kindOf(y), gx = groupOf ? groupOf[x] : 0, gy = groupOf ? groupOf[y] : 0;
+    if (kx != ky) return kx < ky;
+    if (gx != gy) return gx < gy;
+    return length(x) < length(y);
+  });
+  TilePlan P;
+  int kindOfPrev = -1, groupOfPrev = -1, fill = 0;
+  for (int r = 0; r < nB; r++) {
+    const int j = order[r], kind = kindOf(j), g = groupOf ? groupOf[j] : 0;
+    if (kind != kindOfPrev || g != groupOfPrev || fill == kKindQueries[kind]) {
+      if (kind != kindOfPrev) kindStart[kind] = (int)P.group.size();
+      P.q.insert(P.q.end(), kTileSlots, -1);
+      P.len.insert(P.len.end(), kTileSlots, 0);
+      P.group.push_back(g);
+      kindCount[kind]++;
+      kindOfPrev = kind;
+      groupOfPrev = g;
+      fill = 0;
+    }
+    P.q[P.q.size() - kTileSlots + fill] = j;
+    P.len[P.len.size() - kTileSlots + fill] = length(j);
+    fill++;
+  }
+  return P;
+}
+
 // Offsets of every array in the staging/device buffer; needs L's panel and tile counts.
 // rawBytes < 0: the host fills the panels and everything up to the tables is
 // copied.  rawBytes >= 0: the device fills them from the raw option bytes, so
@@ -1383,7 +1599,8 @@ void lay_out(Layout &L, int64_t panelU4, int64_t rawBytes = -1) {
   L.oPanelBlocks = take(sizeof(int) * (size_t)L.nPanels);
   if (!deviceFill) L.oLenSorted = take(lenBytes);
   L.oPerm = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
-  if (L.nGroups > 0) L.oGroup = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
+  if (L.nGroups > 0 && !L.names) L.oGroup = take(sizeof(int) * (size_t)L.nPanels * SLOTS);
+  if (L.names) L.oTileGroup = take(sizeof(int) * (size_t)L.nTiles);
   L.oTileQ = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
   L.oTileLen = take(sizeof(int) * (size_t)L.nTiles * kTileSlots);
   for (int k = 0; k < NKINDS; k++) L.kindTableOff[k] = take(kKindTableBytes[k] * (size_t)L.kindCount[k]);
@@ -1474,8 +1691,10 @@ void fill_groups(const PanelPlan &P, int nA, const int32_t *groupOf, const Layou
 }
 
 // Everything up to (not including) the H2D copy.  Returns 0 or an error code.
+// `names`: the names route, where the panel side (opts) is the names, the tile
+// side (qs) the options and groupOf the options' groups (nullptr: one group).
 int prepare(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *groupOf, int nGroups, const uint8_t *qs,
-            const int64_t *offB, int nB, Arena &ar, Layout &L) {
+            const int64_t *offB, int nB, Arena &ar, Layout &L, bool names = false) {
   if (!query_lengths_ok(offB, nB)) return -2;
   const int nt = host_threads();
   uint8_t code[256];
@@ -1487,10 +1706,12 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *gro
   uint8_t stored[256];
   for (int b = 0; b < 256; b++) stored[b] = L.scaled ? (uint8_t)(code[b] * 4) : code[b];
 
-  const PanelPlan panels = plan_panels(offA, nA, groupOf, nGroups);
-  L.nGroups = groupOf ? nGroups : 0;
+  const PanelPlan panels = names ? plan_panels(offA, nA) : plan_panels(offA, nA, groupOf, nGroups);
+  L.names = names;
+  L.nGroups = names ? std::max(nGroups, 1) : groupOf ? nGroups : 0;
   L.nPanels = (int)panels.blocks.size();
-  const TilePlan tiles = plan_tiles(offB, nB, L.kindStart, L.kindCount);
+  const TilePlan tiles = names ? plan_tiles_grouped(offB, nB, groupOf, L.kindStart, L.kindCount)
+                               : plan_tiles(offB, nB, L.kindStart, L.kindCount);
   L.nTiles = (int)(tiles.q.size() / kTileSlots);
   lay_out(L, panels.off[L.nPanels]);
   if (int rc = ar.ensure(L.bytes)) return rc;
@@ -1498,7 +1719,8 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *gro
   char *h = ar.host;
   memcpy(h + L.oPanelOff, panels.off.data(), sizeof(int64_t) * panels.off.size());
   memcpy(h + L.oPanelBlocks, panels.blocks.data(), sizeof(int) * panels.blocks.size());
-  if (L.nGroups > 0) fill_groups(panels, nA, groupOf, L, h);
+  if (L.nGroups > 0 && !names) fill_groups(panels, nA, groupOf, L, h);
+  if (names) memcpy(h + L.oTileGroup, tiles.group.data(), sizeof(int) * tiles.group.size());
   fill_panels(opts, offA, nA, panels, stored, nt, reinterpret_cast<uint4 *>(h + L.oPanels),
               reinterpret_cast<int *>(h + L.oPerm), reinterpret_cast<int *>(h + L.oLenSorted));
   memcpy(h + L.oTileQ, tiles.q.data(), sizeof(int) * tiles.q.size());
@@ -1515,7 +1737,7 @@ int prepare(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *gro
 // ones, the surplus blocks hold code 0.  It reads the option bytes once, to
 // count them, and copies them once.
 int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *groupOf, int nGroups,
-                 const uint8_t *qs, const int64_t *offB, int nB, int mode, Arena &ar, Layout &L) {
+                 const uint8_t *qs, const int64_t *offB, int nB, int mode, Arena &ar, Layout &L, bool names = false) {
   uint8_t sym[256];
   symbol_table(mode, sym);
   std::vector<uint8_t> nq;
@@ -1539,10 +1761,12 @@ int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const int32_t
   L.nB = nB;
   L.scaled = 1;
 
-  const PanelPlan panels = plan_panels(offA, nA, groupOf, nGroups);
-  L.nGroups = groupOf ? nGroups : 0;
+  const PanelPlan panels = names ? plan_panels(offA, nA) : plan_panels(offA, nA, groupOf, nGroups);
+  L.names = names;
+  L.nGroups = names ? std::max(nGroups, 1) : groupOf ? nGroups : 0;
   L.nPanels = (int)panels.blocks.size();
-  const TilePlan tiles = plan_tiles(nOffB.data(), nB, L.kindStart, L.kindCount);
+  const TilePlan tiles = names ? plan_tiles_grouped(nOffB.data(), nB, groupOf, L.kindStart, L.kindCount)
+                               : plan_tiles(nOffB.data(), nB, L.kindStart, L.kindCount);
   L.nTiles = (int)(tiles.q.size() / kTileSlots);
   lay_out(L, panels.off[L.nPanels], offA[nA]);
   if (int rc = ar.ensure(L.bytes)) return rc;
@@ -1550,7 +1774,8 @@ int prepare_norm(const uint8_t *opts, const int64_t *offA, int nA, const int32_t
   char *h = ar.host;
   memcpy(h + L.oPanelOff, panels.off.data(), sizeof(int64_t) * panels.off.size());
   memcpy(h + L.oPanelBlocks, panels.blocks.data(), sizeof(int) * panels.blocks.size());
-  if (L.nGroups > 0) fill_groups(panels, nA, groupOf, L, h);
+  if (L.nGroups > 0 && !names) fill_groups(panels, nA, groupOf, L, h);
+  if (names) memcpy(h + L.oTileGroup, tiles.group.data(), sizeof(int) * tiles.group.size());
   int *perm = reinterpret_cast<int *>(h + L.oPerm);
   memcpy(perm, panels.order.data(), sizeof(int) * (size_t)nA);
   std::fill(perm + nA, perm + (size_t)L.nPanels * SLOTS, -1);
@@ -1584,12 +1809,37 @@ T *dev_at(const Arena &ar, size_t off) {
   return reinterpret_cast<T *>(ar.dev + off);
 }
 
+// The names route's grid: over panels alone.  Up to kNamesMaxGrid panels get a
+// workgroup each (they differ in length, the hardware balances them, and
+// staging <= 32 KiB of tables per workgroup is a few percent of one panel's
+// work); beyond that the workgroups are persistent and stride, x a multiple of
+// 8 for the XCD remap.
+constexpr int kNamesMaxGrid = 4096;
+int names_grid_x(int nPanels) { return nPanels <= kNamesMaxGrid ? std::max(nPanels, 1) : kNamesMaxGrid; }
+
+// One class's tiles of a names request: one launch, the tile loop is the kernel's.
+template <int KIND, bool SCALED, int METRIC>
+int launch_names_kind(const Layout &L, const Arena &ar, hipStream_t s) {
+  const int count = L.kindCount[KIND], tile0 = L.kindStart[KIND];
+  if (count == 0) return 0;
+  hipLaunchKernelGGL((ed_closest_names_kernel<KIND, SCALED, METRIC>), dim3(names_grid_x(L.nPanels)), dim3(THREADS), 0,
+                     s, dev_at<const uint4>(ar, L.oPanels), dev_at<const int64_t>(ar, L.oPanelOff),
+                     dev_at<const int>(ar, L.oPanelBlocks), dev_at<const int>(ar, L.oLenSorted),
+                     dev_at<const int>(ar, L.oPerm), dev_at<const uint4>(ar, L.tileTable(KIND, tile0)),
+                     dev_at<const int>(ar, L.oTileQ) + (size_t)tile0 * kTileSlots,
+                     dev_at<const int>(ar, L.oTileLen) + (size_t)tile0 * kTileSlots,
+                     dev_at<const int>(ar, L.oTileGroup) + tile0, count, L.nPanels, L.nGroups,
+                     dev_at<u64>(ar, L.oBest));
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
 // One class's tiles: the matrix kernels when `out` is set, the grouped closest
 // kernels for a grouped request, the top-k kernels for a top-k request (slab t
 // writes its tiles' partial lists behind those of the slabs before it), the
 // closest kernels otherwise.
 template <int KIND, bool SCALED, int METRIC>
 int launch_kind(const Layout &L, const Arena &ar, int *out, hipStream_t s) {
+  if (L.names) return launch_names_kind<KIND, SCALED, METRIC>(L, ar, s);
   const int count = L.kindCount[KIND];
   if (count == 0) return 0;
   const int gx = grid_x(L.nPanels, count);
@@ -1719,23 +1969,32 @@ void record_times(Arena &ar, double prep, bool deviceFill) {
 //   D2H copy                             -7  } skipped, the stream is synchronised
 //   stream synchronise                   -6 (when nothing failed before)
 // Timings are recorded on success only.
+// `names` is the names route (ed_closest_names_kernel): opts / nA are then the
+// names (the panel side, any length), qs / nB the options (the tile side, the
+// 256-byte limit and -2 are theirs), groupOf the options' groups (nullptr: one
+// group), and bestIdx / bestDist name-major [nA * nGroups], indices into the
+// options; without options every entry is -1 / -1.
 int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
         int32_t *outT, int32_t *bestIdx, int32_t *bestDist, int mode = MODE_NONE, int metric = METRIC_INDEL2,
-        const int32_t *groupOf = nullptr, int nGroups = 0, bool topk = false, int k = 0) {
+        const int32_t *groupOf = nullptr, int nGroups = 0, bool topk = false, int k = 0, bool names = false) {
   if (mode != MODE_NONE && mode != MODE_ALNUM_LOWER) return -9;
   if (metric != METRIC_INDEL2 && metric != METRIC_LEVENSHTEIN) return -10;
   if (groupOf) {
     if (nGroups < 1) return -11;
-    for (int i = 0; i < nA; i++)
+    for (int i = 0; i < (names ? nB : nA); i++)
       if (groupOf[i] < 0 || groupOf[i] >= nGroups) return -11;
   }
   if (topk && (k < 1 || k > K_MAX)) return -12;
-  const size_t nBest = (size_t)std::max(nB, 0) * (size_t)(topk ? k : groupOf ? nGroups : 1);
+  if (names && !groupOf) nGroups = 1;
+  // who asks and what they choose among: the queries and the options, on the
+  // names route the names (the panel side there) and the options (the tile side)
+  const int nAsk = names ? nA : nB, nPick = names ? nB : nA;
+  const size_t nBest = (size_t)std::max(nAsk, 0) * (size_t)(topk ? k : groupOf || names ? nGroups : 1);
   const bool deviceFill = mode != MODE_NONE;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return -1;
-  if (nB <= 0 || (outT && nA <= 0)) return 0;
-  if (nA <= 0) {
+  if (nAsk <= 0 || (outT && nPick <= 0)) return 0;
+  if (nPick <= 0) {
     for (size_t j = 0; j < nBest; j++) bestIdx[j] = -1, bestDist[j] = -1;
     return 0;
   }
@@ -1744,8 +2003,8 @@ int run(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, con
   const double t0 = now_ms();
   Layout L;
   L.k = topk ? k : 0;
-  int rc = deviceFill ? prepare_norm(opts, offA, nA, groupOf, nGroups, qs, offB, nB, mode, ar, L)
-                      : prepare(opts, offA, nA, groupOf, nGroups, qs, offB, nB, ar, L);
+  int rc = deviceFill ? prepare_norm(opts, offA, nA, groupOf, nGroups, qs, offB, nB, mode, ar, L, names)
+                      : prepare(opts, offA, nA, groupOf, nGroups, qs, offB, nB, ar, L, names);
   if (rc) return rc;
   if (outT && (rc = ar.ensure_out(sizeof(int) * (size_t)nA * nB))) return rc;
   if (topk && (rc = ar.ensure_out(sizeof(u64) * L.partKeys))) return rc;
@@ -1848,6 +2107,21 @@ int m2k_ed_closest_grouped(const uint8_t *opts, const int64_t *offA, int nA, con
 int m2k_ed_closest_k(const uint8_t *opts, const int64_t *offA, int nA, const uint8_t *qs, const int64_t *offB, int nB,
                      int k, int mode, int metric, int32_t *bestIdx, int32_t *bestDist) {
   return run(opts, offA, nA, qs, offB, nB, nullptr, bestIdx, bestDist, mode, metric, nullptr, 0, true, k);
+}
+
+// Many names against a few options: m2k_ed_closest_grouped's answer with the
+// sides' roles swapped on the device (the names in the lanes, the options'
+// tables in LDS), for nB much larger than nA.  bestIdx / bestDist are laid out
+// exactly as there: [nB * nGroups], name-major, indices into the flat options,
+// -1 / -1 for a group without options; groupOf == nullptr is one group (nGroups
+// is then ignored).  The 256-byte limit is on the options here (-2; in a
+// normalising mode after normalisation) and the names may be of any length.
+// Other codes as m2k_ed_closest_grouped.
+int m2k_ed_closest_names(const uint8_t *opts, const int64_t *offA, int nA, const int32_t *groupOf, int nGroups,
+                         const uint8_t *names, const int64_t *offB, int nB, int mode, int metric, int32_t *bestIdx,
+                         int32_t *bestDist) {
+  return run(names, offB, nB, opts, offA, nA, nullptr, bestIdx, bestDist, mode, metric, groupOf, nGroups, false, 0,
+             true);
 }
 
 // prep / H2D / kernel / D2H milliseconds of the last successful call

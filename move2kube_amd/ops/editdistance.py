@@ -117,6 +117,54 @@ def _use_gpu(pairs, device, queries, normalize=None):
     return pairs >= GPU_MIN_PAIRS_COLD or _gpu_warm()
 
 
+# The names route (``gpu.ed_closest_names``): a few options against very many
+# queries run with the sides' roles swapped on the device.  It is taken only
+# after ``_use_gpu`` has chosen the GPU, so limits, fallbacks and exceptions are
+# those of the functions below (``_names_fn`` keeps a request that today's route
+# would refuse on today's route), and the answers are the same by construction.
+# Constants from the sweeps on MI355X (docs/history.md, "Many names against a
+# few options"): at 16, 64 and 256 options the route's end-to-end range lay
+# wholly below today's from 64 queries per option on, grouped or not, and at 16
+# per option it did not; 1024 and 4096 options were measured at 1M names only,
+# so the bound on the options stays at the largest count swept over both.
+# The sweep over the name count was made with ``normalize="alnum_lower"`` (the
+# device fills the panels) and costs (1, 1, 2); costs (1, 1, 1) were measured
+# at the rule's edge and at 1M names only: wholly below at 64 queries per option
+# and at 1M, not at every option count at 16 per option.  ``normalize=None`` (the host fills the panels) is routed by the
+# same rule and was not measured.
+NAMES_ROUTE_MAX_OPTIONS = 256
+NAMES_ROUTE_MIN_QUERIES_PER_OPTION = 64
+
+
+def names_route(na, nb):
+    """Whether ``na`` options against ``nb`` queries go to the names kernels."""
+    return 0 < na <= NAMES_ROUTE_MAX_OPTIONS and nb >= NAMES_ROUTE_MIN_QUERIES_PER_OPTION * na
+
+
+def _names_fn(gpu, options, queries, normalize):
+    """``gpu.ed_closest_names`` when the request is of the names route's shape
+    and the kernel library (or a stand-in module) has it, else None.  An option
+    over the kernels' limit keeps today's route, which has no limit on them.  So
+    does a query over it: the names kernels would take it, but today's route
+    refuses it, and these functions' exceptions and fallbacks stay as they were.
+    Without ``normalize`` ``_use_gpu`` has checked the queries already; with it
+    the kernel library checks them after normalisation, which only drops
+    characters, so only a query that is over the limit raw is normalised here."""
+    fn = getattr(gpu, "ed_closest_names", None)
+    if fn is None or not names_route(len(options), len(queries)):
+        return None
+    has = getattr(gpu, "has_entry", None)
+    if has is not None and not has("m2k_ed_closest_names"):
+        return None
+    limit = getattr(gpu, "MAX_QUERY_BYTES", 64)
+    if any(len(o.encode("utf-8", "surrogateescape") if isinstance(o, str) else o) > limit for o in options):
+        return None
+    if normalize and max(map(len, queries)) > limit and any(
+            len(q) > limit and len(normalize_alnum_lower(q)) > limit for q in queries):
+        return None
+    return fn
+
+
 # costs = (insertion, deletion, substitution).  The GPU kernels serve two
 # triples: the default (1, 1, 2), whose path is untouched by the argument, and
 # (1, 1, 1), plain Levenshtein distance, under the same dispatch rules.  Every
@@ -200,6 +248,9 @@ def closest_indices(options, queries, device="auto", normalize=None, costs=DEFAU
         gpu = _gpu()
         try:
             kw = _gpu_kwargs(costs)
+            names_fn = _names_fn(gpu, options, queries, normalize)
+            if names_fn is not None:
+                return names_fn(options, queries, mode=gpu.ALNUM_LOWER if normalize else gpu.NO_MODE, **kw)
             return (gpu.ed_closest_normalized(options, queries, **kw) if normalize
                     else gpu.ed_closest(options, queries, **kw))
         except gpu.GpuUnsupportedInput:
@@ -237,9 +288,14 @@ def closest_in_groups(groups, queries, device="auto", normalize=None, costs=DEFA
         gpu = _gpu()
         try:
             first = np.cumsum([0] + sizes[:-1]).astype(np.int32)
-            flat, dist = gpu.ed_closest_grouped(
-                [o for g in groups for o in g], np.repeat(np.arange(ng, dtype=np.int32), sizes), ng, queries,
-                mode=gpu.ALNUM_LOWER if normalize else gpu.NO_MODE, **_gpu_kwargs(costs))
+            flat_options, group_of = [o for g in groups for o in g], np.repeat(np.arange(ng, dtype=np.int32), sizes)
+            mode = gpu.ALNUM_LOWER if normalize else gpu.NO_MODE
+            names_fn = _names_fn(gpu, flat_options, queries, normalize)
+            if names_fn is not None:
+                flat, dist = names_fn(flat_options, queries, group_of, ng, mode=mode, **_gpu_kwargs(costs))
+            else:
+                flat, dist = gpu.ed_closest_grouped(flat_options, group_of, ng, queries, mode=mode,
+                                                    **_gpu_kwargs(costs))
             return np.where(flat < 0, flat, flat - first[None, :]).astype(np.int32), dist
         except gpu.GpuUnsupportedInput:
             if device == "gpu":

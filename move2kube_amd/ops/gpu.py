@@ -107,6 +107,11 @@ def _open_library():
         lib.m2k_ed_closest_k.restype = ctypes.c_int
         lib.m2k_ed_closest_k.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_char_p, i64p, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p]
+    if hasattr(lib, "m2k_ed_closest_names"):   # likewise: many names against a few options
+        lib.m2k_ed_closest_names.restype = ctypes.c_int
+        lib.m2k_ed_closest_names.argtypes = [ctypes.c_char_p, i64p, ctypes.c_int, i32p, ctypes.c_int,
+                                             ctypes.c_char_p, i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             i32p, i32p]
     lib.m2k_ed_last_timings.restype = None
     lib.m2k_ed_last_timings.argtypes = [ctypes.POINTER(ctypes.c_double)]
     lib.m2k_gpu_device_count.restype = ctypes.c_int
@@ -121,6 +126,13 @@ def available():
     except OSError:
         return False
     return lib is not None and lib.m2k_gpu_device_count() > 0
+
+
+def has_entry(name):
+    """Whether the loaded kernel library exports ``name`` (an earlier build named
+    by the benchmark's ``--lib`` lacks the late entry points)."""
+    lib = _load()
+    return lib is not None and hasattr(lib, name)
 
 
 _warm = False
@@ -349,6 +361,44 @@ def ed_closest_k(options, queries, k, mode=NO_MODE, metric=INDEL2):
     rc = fn(a, _ptr(offa, ctypes.c_int64), na, q, _ptr(offb, ctypes.c_int64), nb, k, mode, metric,
             _ptr(idx, ctypes.c_int32), _ptr(dist, ctypes.c_int32))
     _check_norm_rc("m2k_ed_closest_k", rc)
+    return idx, dist
+
+
+def ed_closest_names(options, names, group_of=None, n_groups=1, mode=NO_MODE, metric=INDEL2):
+    """:func:`ed_closest` / :func:`ed_closest_grouped` for a few options against
+    very many names, with the sides' roles swapped on the device: the names fill
+    the lanes and the options' tables sit in LDS.  Returns (index, distance)
+    int32 arrays of shape ``[len(names)]``, or ``[len(names), n_groups]`` with
+    ``group_of`` (one group id in ``[0, n_groups)`` per option); ``index`` is into
+    the flat ``options``, the first of the closest ones, -1 / -1 for a group
+    without options.  Here MAX_QUERY_BYTES limits the *options* (after
+    normalisation under ``mode``); the names may be of any length.  ``mode`` and
+    ``metric`` as in :func:`ed_closest_grouped`."""
+    fn = _metric_fn(_lib_or_raise(), "m2k_ed_closest_names", metric)
+    na, nb = len(options), len(names)
+    groups = None
+    if group_of is not None:
+        groups = np.ascontiguousarray(group_of, dtype=np.int32)
+        if groups.shape != (na,):
+            raise ValueError("group_of needs one group id per option")
+        if n_groups < 1:
+            raise ValueError("n_groups must be >= 1")
+    shape = (nb, n_groups) if groups is not None else (nb,)
+    idx = np.full(shape, -1, dtype=np.int32)
+    dist = np.full(shape, -1, dtype=np.int32)
+    if nb == 0 or na == 0:
+        return idx, dist
+    a, offa, amax = _pack(options)
+    q, offb, _ = _pack(names)
+    if mode == NO_MODE and amax > MAX_QUERY_BYTES:
+        raise GpuUnsupportedInput("options longer than %d bytes are not supported on the names route"
+                                  % MAX_QUERY_BYTES)
+    rc = fn(a, _ptr(offa, ctypes.c_int64), na, _ptr(groups, ctypes.c_int32) if groups is not None else None,
+            n_groups, q, _ptr(offb, ctypes.c_int64), nb, mode, metric, _ptr(idx, ctypes.c_int32),
+            _ptr(dist, ctypes.c_int32))
+    if rc == -11:
+        raise ValueError("m2k_ed_closest_names: group ids must lie in [0, n_groups)")
+    _check_norm_rc("m2k_ed_closest_names", rc)
     return idx, dist
 
 
